@@ -19,6 +19,11 @@ N>1: launched by torch.distributed.run, one rank per GPU; each rank fits its
 own nsub subints (weak scaling, no collective on the fit path).  value =
 all ranks' TOAs / max-over-ranks time.
 
+A plain run does no more than that: set-up, warm-up, the timed steps, the
+line (value, ms_per_step, the roofline of the dominant kernel from the HIP
+events recorded during those steps) and, with --dump-outputs DIR, the last
+step's results as DIR/<name>.npy.  Everything below is measured with --full.
+
 Beside value (N = 1, default config): the legs a caller actually gets --
 ``get_toas`` (GetTOAs.get_TOAs end to end on a registered 10k-subint archive,
 TOA records and .tim text included; device-resident and host-resident input),
@@ -122,8 +127,21 @@ def parse():
     ap.add_argument("--config", default="headline", choices=sorted(CONFIGS))
     ap.add_argument("--nsub", type=int, default=None, help="subints per GPU (override)")
     ap.add_argument("--seed", type=int, default=20240917)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, run everything else the benchmark measures "
+                         "or checks: the CPU baseline and the parity sample against the oracle, "
+                         "the get_toas / ppalign / generic_nbin legs, host-resident input "
+                         "(--host-stream), the 2,000-subint slice of gm_shard.  Off by default: "
+                         "a plain run sets up, warms up, times the steps and prints the line "
+                         "(with the roofline of the HIP events recorded in those same steps; "
+                         "--config ppalign's event-timed call belongs to that config either way)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last "
+                         "step as DIR/<name>.npy (float64; a fixed seeded sample of the subints "
+                         "where the whole is over 60 MB).  The inputs depend on the arguments "
+                         "alone, so two builds can be compared output for output")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="subints the 1-core oracle fits (default per config; 0: skip)")
+                    help="--full: subints the 1-core oracle fits (default per config; 0: skip)")
     ap.add_argument("--cpu-procs", type=int, default=None,
                     help="processes of the all-core CPU baseline (default: every core of "
                          "os.sched_getaffinity within the cgroup CPU quota)")
@@ -131,7 +149,7 @@ def parse():
                     help="CPU work per process of the all-core leg (s)")
     ap.add_argument("--no-timing", action="store_true", help="skip per-kernel HIP events")
     ap.add_argument("--no-legs", action="store_true",
-                    help="headline only: skip the get_toas / ppalign legs")
+                    help="--full, headline only: skip the get_toas / ppalign / generic_nbin legs")
     ap.add_argument("--shard-chunk", type=int, default=None,
                     help="gm_shard: subints generated and fitted per chunk (default 25000); "
                          "gm_shard_host: subints copied, unpacked and fitted per chunk "
@@ -141,8 +159,8 @@ def parse():
     ap.add_argument("--no-spec-cache", action="store_true",
                     help="--config ppalign: align without the data-spectrum cache (A/B)")
     ap.add_argument("--host-stream", type=int, default=None,
-                    help="also time host-resident (pinned) input streamed over PCIe in chunks "
-                         "of this many subints (default: on for config gm; 0: off)")
+                    help="--full: also time host-resident (pinned) input streamed over PCIe in "
+                         "chunks of this many subints (default: on for config gm; 0: off)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="libppfit launch-schedule option (ppf_set_option, _lib.OPTIONS); "
                          "no option changes a result")
@@ -150,7 +168,16 @@ def parse():
                     help="launcher check without a GPU: every rank runs the timing and "
                          "reduction code around a no-op step over gloo (tests only; the line "
                          "says so and is not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run measures value alone: what else the benchmark does is
+        # asked for with --full, never switched on by an option of its own
+        if args.cpu_sample or args.host_stream:
+            ap.error("--cpu-sample / --host-stream above 0 need --full")
+        args.cpu_sample, args.host_stream, args.no_legs = 0, 0, True
+    return args
 
 
 def free_port():
@@ -245,6 +272,33 @@ def timing_ratio(config):
         return None
     rec = json.load(open(f)).get(TIMING_KEY.get(config, config))
     return None if rec is None else rec["ratio_oracle_over_reference"]
+
+
+DUMP_LIMIT = 60 * 10 ** 6  # array bytes --dump-outputs writes at most (files: under 64 MB)
+
+
+def dump_outputs(path, arrays, nrows=None):
+    """--dump-outputs: arrays ({name: numpy array}) as path/<name>.npy in
+    float64.  Over DUMP_LIMIT in all, the arrays whose first axis is nrows
+    (one row per subint) keep a fixed seeded sample of the rows -- the same
+    rows of every array, listed in sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        per_row = [k for k, a in arrays.items() if nrows and a.ndim and a.shape[0] == nrows]
+        fixed = total - sum(arrays[k].nbytes for k in per_row)
+        row_bytes = sum(arrays[k].nbytes // nrows for k in per_row) + 8
+        keep = (DUMP_LIMIT - fixed) // row_bytes if per_row else 0
+        if keep < 1:
+            raise SystemExit("--dump-outputs: %d bytes of outputs and no per-subint rows to "
+                             "sample" % total)
+        rows = np.sort(np.random.default_rng(64).choice(nrows, size=keep, replace=False))
+        for k in per_row:
+            arrays[k] = arrays[k][rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def synth_inputs(eng, config, nsub, seed, sub0):
@@ -401,7 +455,7 @@ def leg_ppalign(eng, narch, niter, seed):
             "phase_s": {k: round(v, 4) for k, v in phases.items() if k != "start"},
             "kernel_ms_per_iteration": {k: round(v[0] / niter, 4) for k, v in ktimes.items()},
             "kernel_launches": {k: v[1] for k, v in ktimes.items()},
-            "_ktimes": ktimes,
+            "_ktimes": ktimes, "_port": port,
             "workload": "config 5: %d archives x 1 subint x %d chan x %d bin, fit_dm, niter %d; "
                         "archives registered once beforehand (register_archives); opening "
                         "them and the unit stack inside the timed call"
@@ -551,6 +605,11 @@ def main():
             ktimes[name] = eng.kernel_time(name)
         eng.set_timing(False)
     status, nfev = host["status"], host["nfev"]
+    if args.dump_outputs and rank == 0:
+        # the last timed step's fit_batch results, every key (the per-TOA
+        # ones the step copied to the host are among them)
+        from pulseportraiture_amd.engine import results_to_host
+        dump_outputs(args.dump_outputs, results_to_host(out, None, eng.stream), nsub)
 
     # ---- PCIe-inclusive rate (config gm): the same subints from pinned host
     # memory, copies overlapped with the fits; reported beside value ----
@@ -593,6 +652,7 @@ def main():
         legs["get_toas_host"], _ = leg_get_toas(eng, w, data, reps=1, host=True)
         legs["generic_nbin"] = leg_generic_nbin(eng, args.seed)
         legs["ppalign"] = leg_ppalign(eng, args.ppalign_narch, args.ppalign_niter, args.seed)
+        del legs["ppalign"]["_port"]
         from pulseportraiture_amd import ppalign as _ppa
         legs["ppalign"]["roofline"] = ppalign_roofline(
             legs["ppalign"].pop("_ktimes"), args.ppalign_narch, args.ppalign_niter,
@@ -861,22 +921,27 @@ def main_gm_shard(args, eng, rank, world):
     fit_ms = sum(c.elapsed_time(d) for _, _, c, d in ev)
     status = host["status"].numpy()
     nfev = host["nfev"].numpy()
-    # the 2,000-subint slice (--config gm's step) in the same process
-    wS, dS, kwS, _ = synth_inputs(eng, "gm", 2000, args.seed, base)
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.numpy() for k, v in host.items()}, N)
+    # the 2,000-subint slice (--config gm's step) in the same process (--full)
+    slice_ms = None
+    if args.full:
+        wS, dS, kwS, _ = synth_inputs(eng, "gm", 2000, args.seed, base)
+        torch.cuda.synchronize()
 
-    def sstep():
-        return eng.fit_batch(dS, kwS["model"], kwS["freqs"], kwS["P"], kwS["init"], flags,
-                             nu_fit=kwS["nu"], guess=True, guess_Ns=100)
-    for _ in range(2):
-        sstep()
-    torch.cuda.synchronize()
-    ts0 = time.perf_counter()
-    for _ in range(10):
-        sstep()
-    torch.cuda.synchronize()
-    slice_ms = (time.perf_counter() - ts0) / 10 * 1e3
-    del dS, bufs, buf
+        def sstep():
+            return eng.fit_batch(dS, kwS["model"], kwS["freqs"], kwS["P"], kwS["init"], flags,
+                                 nu_fit=kwS["nu"], guess=True, guess_Ns=100)
+        for _ in range(2):
+            sstep()
+        torch.cuda.synchronize()
+        ts0 = time.perf_counter()
+        for _ in range(10):
+            sstep()
+        torch.cuda.synchronize()
+        slice_ms = (time.perf_counter() - ts0) / 10 * 1e3
+        del dS
+    del bufs, buf
     geng.close()
     if rank != 0:
         if world > 1:
@@ -913,10 +978,11 @@ def main_gm_shard(args, eng, rank, world):
                    "(two buffers); generate_ms / fit_ms are each side's own event time",
         "fit_only_value": round(N / (fit_ms / 1e3), 2),
         "per_toa_us": round(per_toa_us, 4), "fit_only_per_toa_us": round(fit_ms * 1e3 / N, 4),
-        "slice_2000": {"ms_per_step": round(slice_ms, 3),
-                       "per_toa_us": round(slice_ms * 1e3 / 2000, 4),
-                       "value": round(2000 / slice_ms * 1e3, 2)},
-        "fit_only_over_slice_per_toa": round(fit_ms / N / (slice_ms / 2000), 4),
+        "slice_2000": None if slice_ms is None else {
+            "ms_per_step": round(slice_ms, 3), "per_toa_us": round(slice_ms * 1e3 / 2000, 4),
+            "value": round(2000 / slice_ms * 1e3, 2)},
+        "fit_only_over_slice_per_toa": None if slice_ms is None else round(
+            fit_ms / N / (slice_ms / 2000), 4),
         "status_counts": {str(k): int(v) for k, v in zip(*np.unique(status, return_counts=True))},
         "mean_nfev": float(np.mean(nfev)), "parity_sample": parity,
     }
@@ -1072,6 +1138,8 @@ def main_gm_shard_host(args, eng, rank, world):
     status = host["status"].numpy()
     nfev = host["nfev"].numpy()
     del draw, fbuf, hraw
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.numpy() for k, v in host.items()}, N)
     if rank != 0:
         if world > 1:
             torch.distributed.destroy_process_group()
@@ -1127,11 +1195,17 @@ def main_get_toas(args, eng, rank, world, w, data, step, desc):
                          "torch.distributed is initialised; see tests)")
     steps = max(1, args.steps)
     g, gt = leg_get_toas(eng, w, data, reps=steps)
-    out, host = step()
-    same = float(np.max(np.abs(np.asarray(gt.phis[0]) - host["params"][:, 0]) /
-                        host["param_errs"][:, 0]))
-    gh, _ = leg_get_toas(eng, w, data, reps=1, host=True)
     nsub = data.shape[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: getattr(gt, k)[0] for k in
+                                         ("phis", "phi_errs", "DMs", "DM_errs", "TOA_errs")}, nsub)
+    # beside value (--full): the same subints through fit_batch, and from host memory
+    same = gh = None
+    if args.full:
+        out, host = step()
+        same = float(np.max(np.abs(np.asarray(gt.phis[0]) - host["params"][:, 0]) /
+                            host["param_errs"][:, 0]))
+        gh, _ = leg_get_toas(eng, w, data, reps=1, host=True)
     line = {"metric": "TOAs/sec (GetTOAs.get_TOAs end to end, 64ch×2048bin phase+DM fp64)",
             "value": g["value"], "unit": "TOAs/s", "n_gpus": 1, "steps": steps, "warmup": 1,
             "ms_per_step": g["ms_per_call"], "higher_is_better": True, "scaling": "weak",
@@ -1218,6 +1292,9 @@ def main_ppalign(args, eng, rank, world):
     cache = ppalign.SPEC_CACHE
     r = leg_ppalign(eng, narch, args.ppalign_niter, args.seed)
     kt = r.pop("_ktimes")
+    port = r.pop("_port")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"template": port})
     r["spec_cache"] = cache
     roof = ppalign_roofline(kt, narch, args.ppalign_niter, cache)
     line = {"metric": "archive-iterations/sec (ppalign.align_archives, 256ch×2048bin fp64)",

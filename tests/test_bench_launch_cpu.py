@@ -33,6 +33,44 @@ def test_bench_gpus2_launches_two_ranks_one_line():
     assert d["ms_per_step"] == max(d["rank_ms_per_step"])
 
 
+def test_bench_extras_need_full():
+    """--cpu-sample / --host-stream ask for what only --full measures."""
+    bench = os.path.join(ROOT, "bench.py")
+    for extra in (["--cpu-sample", "5"], ["--host-stream", "100"]):
+        p = subprocess.run([sys.executable, bench, "--dry-run"] + extra, capture_output=True,
+                           text=True, timeout=60)
+        assert p.returncode == 2 and "--full" in p.stderr
+    d = json.loads(_run(["--dry-run", "--full", "--cpu-sample", "5", "--steps", "1"])[0])
+    assert d["steps"] == 1
+
+
+def test_dump_outputs_float64_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 .npy; over the byte limit the per-subint
+    arrays keep the same seeded rows, the same from call to call."""
+    import numpy as np
+    import bench
+    n = 1000
+    arrays = {"params": np.arange(n * 5.0).reshape(n, 5), "status": np.arange(n, dtype=np.int32),
+              "template": np.ones(7, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, n)
+    for k, a in arrays.items():
+        got = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10000)
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), arrays, n)
+    got = {f[:-4]: np.load(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))}
+    assert sorted(got) == ["params", "sample_rows", "status", "template"]
+    rows = got["sample_rows"].astype(int)
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["params"], arrays["params"][rows])
+    assert np.array_equal(got["status"], arrays["status"][rows])
+    assert np.array_equal(got["template"], arrays["template"])
+    assert sum(a.nbytes for a in got.values()) <= 10000
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(str(tmp_path / "s2" / (k + ".npy")))), k
+
+
 def test_bench_gpus1_stays_in_process():
     d = json.loads(_run(["--dry-run", "--steps", "1", "--warmup", "0"])[0])
     assert d["n_gpus"] == 1 and len(d["rank_pids"]) == 1

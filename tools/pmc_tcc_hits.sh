@@ -7,7 +7,7 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp || exit 1
-case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
+case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--full --nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
 timeout -s KILL 240 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum -d $O/tcc_$CFG -o run --output-format csv -- python3 $R/bench.py --config $CFG $P > $O/tcc_$CFG.log 2>&1 \
   || { echo "pmc failed"; tail -3 $O/tcc_$CFG.log; exit 1; }
 python3 - $O/tcc_$CFG <<'PY'

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 cd /tmp || exit 1
 B="$R/bench.py --config $CFG"
 S=${V:+_$V}
-case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
+case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--full --nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 200 rocprofv3 --pmc $c -d $O/pmc_${CFG}${S}_$c -o run --output-format csv -- python3 $B $P > $O/pmc_${CFG}${S}_$c.log 2>&1 \
     || { echo "pmc $c failed"; tail -3 $O/pmc_${CFG}${S}_$c.log; exit 1; }

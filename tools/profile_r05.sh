@@ -16,7 +16,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp || exit 1
 B="$R/bench.py --config $CFG"
-case $CFG in ppalign) RUN="--cpu-sample 0";; *) RUN="--steps 10 --warmup 2 --cpu-sample 0";; esac
+case $CFG in ppalign) RUN="--cpu-sample 0";; *) RUN="--full --steps 10 --warmup 2 --cpu-sample 0";; esac
 timeout -k 10 400 python3 $B $RUN > $O/bench_$CFG.log 2>&1 || { echo "bench failed"; tail -5 $O/bench_$CFG.log; exit 1; }
 tail -c 300 $O/bench_$CFG.log
 LEGS="--no-legs"; [ $CFG = ppalign ] && LEGS=""
@@ -24,7 +24,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace_$CFG -o run --out
 find $O/trace_$CFG -name "*kernel_stats.csv" -exec head -6 {} \;
 [ "$NF" = "0" ] && NF=$(case $CFG in headline) echo 10000;; gm) echo 2000;; ppalign) echo 4096;; *) echo 1000;; esac)
 pmc() {  # pmc NAME "COUNTERS"
-  case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
+  case $CFG in ppalign) P="--nsub $NF --cpu-sample 0";; *) P="--full --nsub $NF --steps 1 --warmup 0 --cpu-sample 0 --no-timing --no-legs";; esac
   timeout -s KILL 200 rocprofv3 --pmc $2 -d $O/pmc_${CFG}_$1 -o run --output-format csv -- python3 $B $P > $O/pmc_${CFG}_$1.log 2>&1 || { echo "pmc $1 failed"; tail -3 $O/pmc_${CFG}_$1.log; return 1; }
   echo "pmc $1 ok"
 }
