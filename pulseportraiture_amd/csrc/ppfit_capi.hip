@@ -36,6 +36,21 @@ struct Buffer {
   size_t bytes = 0;
 };
 
+// the device buffers of a context (ppf_ctx::buf), each grown on demand (ensure)
+enum BufferId {
+  kWs,     // per-chunk fit workspace
+  kMspec,  // template spectra
+  kAux,    // misc (synth templates, partial sums)
+  kMmean,  // mean template spectra (guess)
+  kPtime,  // k_fit_taylor phase clocks (ppf_phase_profile)
+  kSpart,  // split scattering solve: block partials + running count
+  kTmpl,   // template builders: knots / coefficients, rows and spectra
+  kNumBuffers
+};
+
+using TableCache = std::vector<std::pair<int, double2*>>;  // (nbin, table)
+constexpr size_t kUnknown = ~(size_t)0;
+
 }  // namespace
 
 struct ppf_ctx {
@@ -43,17 +58,11 @@ struct ppf_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   int64_t ws_limit = (int64_t)32 << 30;
-  double2* tw[16] = {nullptr};
-  double2* vp[16] = {nullptr};  // moment power tables (k_vpow)
-  // the same two tables for nbin that are not powers of two
-  std::vector<std::pair<int, double2*>> tw_gen, vp_gen;
-  Buffer ws;     // per-chunk fit workspace
-  Buffer mspec;   // template spectra
-  Buffer aux;     // misc (synth templates, partial sums)
-  Buffer mmean;   // mean template spectra (guess)
-  Buffer ptime;   // k_fit_taylor phase clocks (ppf_phase_profile)
-  Buffer spart;   // split scattering solve: block partials + running count
-  Buffer tmpl;    // template builders: knots / coefficients, rows and spectra
+  // rfft twiddles and moment power tables (k_vpow), one per nbin (table_for)
+  TableCache tw, vp;
+  Buffer buf[kNumBuffers];
+  // static LDS of k_fit_taylor on this context's device (taylor_lds_moments)
+  size_t taylor_static_lds = kUnknown;
   int* active_h = nullptr;  // pinned host copies of the running count (two in flight)
   hipEvent_t scat_ev[2] = {nullptr, nullptr};  // their copies' completion
   hipStream_t stream2 = nullptr;        // second queue of the piece pipeline
@@ -110,34 +119,15 @@ int check_nbin_any(ppf_ctx* ctx, int nbin, int* logN) {
 
 // dynamic LDS of the generic-length kernels
 size_t gen_row_lds(int nbin) { return (size_t)nbin * sizeof(double); }
+size_t gen_spec_lds(int nbin) { return (size_t)(nbin / 2 + 1) * sizeof(double2); }
 size_t gen_rot_lds(int nbin) {
-  return (((size_t)nbin * sizeof(double) + 15) & ~(size_t)15) + (size_t)(nbin / 2 + 1) * sizeof(double2);
+  return (((size_t)nbin * sizeof(double) + 15) & ~(size_t)15) + gen_spec_lds(nbin);
 }
 
-// the generic-length data pass of n subints: every row's rfft on the matrix
-// cores into the X rows, then the per-subint pass (ppfit_generic.hip)
-// (data-spectrum cache: the spectra into the cache's rows under STORE; under
-// USE they are there already)
-void launch_data_gen(const SpecArgs& sa, int n, int nbin, hipStream_t st) {
-  const int nrows = n * sa.nchan, NH = nbin / 2 + 1;
-  const double* rows = sa.data + (size_t)sa.sub0 * sa.nchan * nbin;
-  const dim3 g((nrows + kGenRows - 1) / kGenRows, (NH + 255) / 256);
-  double2* dst = sa.D ? sa.D : sa.X;
-  if (sa.spec_mode != PPF_SPEC_USE) {
-    if (nbin <= kGenLdsTw)
-      hipLaunchKernelGGL(k_dft_rows_mfma<true>, g, dim3(kBlock), dft_mfma_lds(nbin, true), st,
-                         rows, dst, nrows, nbin, sa.NHP, sa.tw);
-    else
-      hipLaunchKernelGGL(k_dft_rows_mfma<false>, g, dim3(kBlock), dft_mfma_lds(nbin, false), st,
-                         rows, dst, nrows, nbin, sa.NHP, sa.tw);
-  }
-  hipLaunchKernelGGL(k_data_post_gen, dim3(n), dim3(kBlock), 0, st, sa, nbin);
-}
-
-// the table of nbin in a generic-length cache (created by make on first use)
+// the table of nbin in a cache (n cells, created by make on first use)
 template <typename F>
-int gen_table(ppf_ctx* ctx, std::vector<std::pair<int, double2*>>& cache, int nbin, size_t n,
-              F&& make, const double2** out) {
+int table_for(ppf_ctx* ctx, TableCache& cache, int nbin, size_t n, F&& make,
+              const double2** out) {
   for (auto& p : cache)
     if (p.first == nbin) { *out = p.second; return PPF_OK; }
   double2* t = nullptr;
@@ -173,29 +163,16 @@ int ensure(ppf_ctx* ctx, Buffer& b, size_t bytes) {
 }
 
 int twiddles(ppf_ctx* ctx, int nbin, const double2** out) {
-  const int l = ilog2_exact(nbin);
-  if (l < 0)
-    return gen_table(ctx, ctx->tw_gen, nbin, (size_t)nbin, [&](double2* t) {
-      hipLaunchKernelGGL(k_twiddles, dim3((nbin + 255) / 256), dim3(256), 0, ctx->stream, t, nbin);
-    }, out);
-  if (!ctx->tw[l]) {
-    HIPCHK(ctx, hipMalloc(&ctx->tw[l], (size_t)nbin * sizeof(double2)));
-    hipLaunchKernelGGL(k_twiddles, dim3((nbin + 255) / 256), dim3(256), 0, ctx->stream,
-                       ctx->tw[l], nbin);
-    HIPCHK(ctx, hipGetLastError());
-  }
-  *out = ctx->tw[l];
-  return PPF_OK;
+  return table_for(ctx, ctx->tw, nbin, (size_t)nbin, [&](double2* t) {
+    hipLaunchKernelGGL(k_twiddles, dim3((nbin + 255) / 256), dim3(256), 0, ctx->stream, t, nbin);
+  }, out);
 }
-
-void launch_fit_taylor(const ppf_ctx* ctx, dim3 g, size_t lds, hipStream_t st, const FitArgs& fa);
 
 // Moments per channel of T slot 0 that k_fit_taylor's LDS copy holds:
 // kTaylorBlocksPerCU blocks of (static LDS + Meta + nchan * tnl doubles) in a
 // CU's LDS, whole KB per block.
-int taylor_lds_moments(int nchan, size_t lds_meta) {
-  static size_t stat = 0;
-  if (!stat) {
+int taylor_lds_moments(ppf_ctx* ctx, int nchan, size_t lds_meta) {
+  if (ctx->taylor_static_lds == kUnknown) {
     size_t mx = 0;
     const void* ks[4] = {reinterpret_cast<const void*>(&k_fit_taylor<true, false>),
                          reinterpret_cast<const void*>(&k_fit_taylor<false, false>),
@@ -206,8 +183,9 @@ int taylor_lds_moments(int nchan, size_t lds_meta) {
       if (hipFuncGetAttributes(&at, k) != hipSuccess) return 0;
       mx = std::max(mx, at.sharedSizeBytes);
     }
-    stat = mx;
+    ctx->taylor_static_lds = mx;
   }
+  const size_t stat = ctx->taylor_static_lds;
   const size_t per_block = (kLdsPerCU / kTaylorBlocksPerCU) & ~(size_t)1023;
   if (per_block <= stat + lds_meta) return 0;
   const size_t nl = (per_block - stat - lds_meta) / ((size_t)nchan * sizeof(double));
@@ -215,21 +193,11 @@ int taylor_lds_moments(int nchan, size_t lds_meta) {
 }
 
 int vpow_table(ppf_ctx* ctx, int nbin, const double2** out) {
-  const int l = ilog2_exact(nbin);
   const int rows = kVpowRows(nbin / 2);
-  if (l < 0)
-    return gen_table(ctx, ctx->vp_gen, nbin, (size_t)rows * 16, [&](double2* t) {
-      hipLaunchKernelGGL(k_vpow, dim3((rows * 16 + 255) / 256), dim3(256), 0, ctx->stream, t,
-                         nbin, rows);
-    }, out);
-  if (!ctx->vp[l]) {
-    HIPCHK(ctx, hipMalloc(&ctx->vp[l], (size_t)rows * 16 * sizeof(double2)));
-    hipLaunchKernelGGL(k_vpow, dim3((rows * 16 + 255) / 256), dim3(256), 0, ctx->stream,
-                       ctx->vp[l], nbin, rows);
-    HIPCHK(ctx, hipGetLastError());
-  }
-  *out = ctx->vp[l];
-  return PPF_OK;
+  return table_for(ctx, ctx->vp, nbin, (size_t)rows * 16, [&](double2* t) {
+    hipLaunchKernelGGL(k_vpow, dim3((rows * 16 + 255) / 256), dim3(256), 0, ctx->stream, t,
+                       nbin, rows);
+  }, out);
 }
 
 hipEvent_t ev_get(ppf_ctx* ctx) {
@@ -341,25 +309,440 @@ int model_spectra(ppf_ctx* ctx, int nrow, int nbin, const double* model, int zer
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// the first moment pass inside k_fit_taylor (default) or its own k_moments
-// launch (PPF_OPT_FUSE_MOMENTS = 0)
-// launch; the moment passes form X from the data-spectrum cache when fa.Dsp is set
-void launch_fit_taylor(const ppf_ctx* ctx, dim3 g, size_t lds, hipStream_t st, const FitArgs& fa) {
-  const bool mom = ctx->opt[PPF_OPT_FUSE_MOMENTS] != 0;
-  WIDE_SWITCH(fa.gdyn != nullptr, {
-    if (fa.Dsp) {
-      if (mom) hipLaunchKernelGGL((k_fit_taylor<true, true, WD>), g, dim3(kBlock), lds, st, fa);
-      else hipLaunchKernelGGL((k_fit_taylor<false, true, WD>), g, dim3(kBlock), lds, st, fa);
-    } else {
-      if (mom) hipLaunchKernelGGL((k_fit_taylor<true, false, WD>), g, dim3(kBlock), lds, st, fa);
-      else hipLaunchKernelGGL((k_fit_taylor<false, false, WD>), g, dim3(kBlock), lds, st, fa);
+// dynamic LDS of the Meta kernels' per-channel tables
+size_t meta_lds(int nchan) { return align256((size_t)nchan * (5 * sizeof(double) + sizeof(int))); }
+
+// ---------------------------------------------------------------------------
+// Row transforms that several entry points dispatch, nrow rows on st: the
+// generic-length kernel (logN < 0, ppfit_generic.hip) or the <LG> one, each
+// with its dynamic LDS.
+// ---------------------------------------------------------------------------
+void launch_rfft_rows(hipStream_t st, int logN, int nbin, int nrow, const double* in, double2* out,
+                      const double2* tw) {
+  if (logN < 0)
+    hipLaunchKernelGGL(k_rfft_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin), st, in, out,
+                       tw, nbin);
+  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in, out,
+                                       tw));
+}
+
+void launch_irfft_rows(hipStream_t st, int logN, int nbin, int nrow, const double2* in,
+                       double* out, const double2* tw) {
+  if (logN < 0)
+    hipLaunchKernelGGL(k_irfft_rows_gen, dim3(nrow), dim3(kBlock), gen_spec_lds(nbin), st, in, out,
+                       tw, nbin);
+  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_irfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in, out,
+                                       tw));
+}
+
+// rotation by phase and / or scattering by tau (either may be null)
+void launch_rotate_rows(hipStream_t st, int logN, int nbin, int nrow, const double* in,
+                        const double* phase, const double* tau, double* out, const double2* tw) {
+  if (logN < 0)
+    hipLaunchKernelGGL(k_rotate_rows_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin), st, in,
+                       phase, tau, out, tw, nbin);
+  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rotate_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in,
+                                       phase, tau, out, tw));
+}
+
+// ---------------------------------------------------------------------------
+// ppf_fit_portrait_batch: workspace plan, stages, argument binding
+// ---------------------------------------------------------------------------
+
+// Workspace plan of one fit call: the arrays of a chunk of subints one after
+// another in the context's workspace buffer.  Each array's per-subint size is
+// written here and nowhere else.
+struct FitWorkspace {
+  struct Span { size_t off, per; };  // an array's offset and its bytes per subint
+  Span X, R, sig, dsum, st, acc, wsc, T, G;
+  int64_t chunk;         // subints per pass under the workspace limit
+  size_t total;          // bytes of a chunk
+  char* base = nullptr;  // the buffer, once it holds them
+
+  FitWorkspace(int nchan, int NHP, bool taylor, bool wide, int64_t ws_limit, int64_t nsub) {
+    const size_t bX = (size_t)nchan * NHP * sizeof(double2);
+    const size_t bR = (size_t)NHP * sizeof(double2);
+    const size_t bC = (size_t)nchan * sizeof(double);
+    const size_t bAcc = (size_t)2 * nchan * 10 * sizeof(double);
+    const size_t bW = (size_t)nchan * 8 * sizeof(double);
+    const size_t bT = taylor ? (size_t)2 * nchan * kMT * sizeof(double) : 0;
+    // per-channel tables in HBM (the WIDE kernels, ppfit_kernels.hpp chan_tables)
+    const size_t bG = wide ? align256(std::max(meta_lds(nchan), xspec_dyn_lds(nchan))) : 0;
+    // (2 bR: a second R-sized row that no kernel uses; it stays in the plan so
+    // that a workspace limit gives the chunk, and so the launches, it always gave)
+    const size_t per_sub = bX + bT + 2 * bR + 2 * bC + sizeof(SolveState) + bAcc + bW + bG;
+    chunk = std::max<int64_t>(1, std::min<int64_t>(nsub, ws_limit / (int64_t)(per_sub + 1024)));
+    total = 0;
+    auto take = [&](size_t per) {
+      const Span s{total, per};
+      total = align256(total + (size_t)chunk * per);
+      return s;
+    };
+    X = take(bX);
+    R = take(bR);
+    take(bR);
+    sig = take(bC);
+    dsum = take(bC);
+    st = take(sizeof(SolveState));
+    acc = take(bAcc);
+    wsc = take(bW);
+    T = take(bT);
+    G = take(bG);
+  }
+
+  template <typename P>
+  P* at(const Span& s, int sub) const {
+    return reinterpret_cast<P*>(base + s.off + (size_t)sub * s.per);
+  }
+
+  // Every workspace pointer of the two argument structs, for the chunk's
+  // subints sub ..: the whole chunk at sub = 0, a piece of it otherwise.
+  void slice(int sub, SpecArgs& sa, FitArgs& fa) const {
+    fa.X = sa.X = at<double2>(X, sub);
+    fa.R = sa.R = at<double2>(R, sub);
+    fa.sig = sa.sig = at<double>(sig, sub);
+    fa.dsum = sa.dsum = at<double>(dsum, sub);
+    fa.st = at<SolveState>(st, sub);
+    fa.acc = at<double>(acc, sub);
+    fa.wsc = at<double>(wsc, sub);
+    fa.T = T.per ? at<double>(T, sub) : nullptr;
+    fa.gdyn = sa.gdyn = G.per ? at<unsigned char>(G, sub) : nullptr;
+    fa.gdyn_stride = sa.gdyn_stride = G.per;
+  }
+};
+
+// What the stages of one fit call share: the data pass's dispatch and the
+// kernels' dynamic LDS sizes.
+struct FitLaunch {
+  int logN, nbin;
+  bool wide;
+  size_t lds_meta;  // the Meta kernels (none for the WIDE ones)
+  size_t lds_xspec, lds_guess, lds_taylor, lds_scat;
+};
+
+// The stages of a fit over n subints on st, each under its kernel id's event
+// bracket.  Both schedules of ppf_fit_portrait_batch are made of these.
+
+// The data pass.  Generic length: every row's rfft on the matrix cores into
+// the X rows, then the per-subint pass (ppfit_generic.hip) (data-spectrum
+// cache: the spectra into the cache's rows under STORE; under USE they are
+// there already).
+int stage_data(ppf_ctx* ctx, hipStream_t st, int n, const SpecArgs& sa, const FitLaunch& L) {
+  const int nbin = L.nbin;
+  return timed_on(ctx, PPF_K_DATA_XSPEC, st, [&] {
+    if (L.logN < 0) {
+      const int nrows = n * sa.nchan, NH = nbin / 2 + 1;
+      const double* rows = sa.data + (size_t)sa.sub0 * sa.nchan * nbin;
+      const dim3 g((nrows + kGenRows - 1) / kGenRows, (NH + 255) / 256);
+      double2* dst = sa.D ? sa.D : sa.X;
+      if (sa.spec_mode != PPF_SPEC_USE) {
+        if (nbin <= kGenLdsTw)
+          hipLaunchKernelGGL(k_dft_rows_mfma<true>, g, dim3(kBlock), dft_mfma_lds(nbin, true), st,
+                             rows, dst, nrows, nbin, sa.NHP, sa.tw);
+        else
+          hipLaunchKernelGGL(k_dft_rows_mfma<false>, g, dim3(kBlock), dft_mfma_lds(nbin, false),
+                             st, rows, dst, nrows, nbin, sa.NHP, sa.tw);
+      }
+      hipLaunchKernelGGL(k_data_post_gen, dim3(n), dim3(kBlock), 0, st, sa, nbin);
     }
+    LOGN_SWITCH(L.logN, WIDE_SWITCH(L.wide, hipLaunchKernelGGL((k_data_xspec<LG, WD>), dim3(n),
+                                                               dim3(XspecCfg<LG>::WPB * 64),
+                                                               L.lds_xspec, st, sa)));
   });
 }
 
-void launch_moments(dim3 g, hipStream_t st, const FitArgs& fa) {
-  if (fa.Dsp) hipLaunchKernelGGL((k_moments<4, true>), g, dim3(kBlock), 0, st, fa);
-  else hipLaunchKernelGGL((k_moments<4, false>), g, dim3(kBlock), 0, st, fa);
+int stage_guess(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const FitLaunch& L) {
+  return timed_on(ctx, PPF_K_GUESS, st, [&] {
+    if (fa.guess && fa.guess_wave) hipLaunchKernelGGL(k_guess_w, dim3(n), dim3(64), 0, st, fa);
+    hipLaunchKernelGGL(k_guess, dim3(n), dim3(kBlock), fa.guess ? L.lds_guess : 0, st, fa);
+  });
+}
+
+// the first moment pass as its own launch (PPF_OPT_FUSE_MOMENTS = 0; by
+// default it runs inside k_fit_taylor); the moment passes form X from the
+// data-spectrum cache when fa.Dsp is set
+int stage_moments(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa) {
+  if (ctx->opt[PPF_OPT_FUSE_MOMENTS]) return PPF_OK;
+  return timed_on(ctx, PPF_K_MOMENTS, st, [&] {
+    const dim3 g(n, (fa.nchan + 16 * kWaves - 1) / (16 * kWaves));
+    if (fa.Dsp) hipLaunchKernelGGL((k_moments<4, true>), g, dim3(kBlock), 0, st, fa);
+    else hipLaunchKernelGGL((k_moments<4, false>), g, dim3(kBlock), 0, st, fa);
+  });
+}
+
+int stage_taylor(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const FitLaunch& L) {
+  const bool mom = ctx->opt[PPF_OPT_FUSE_MOMENTS] != 0;
+  const dim3 g(n), b(kBlock);
+  const size_t lds = L.lds_taylor;
+  return timed_on(ctx, PPF_K_FIT_TAYLOR, st, [&] {
+    WIDE_SWITCH(L.wide, {
+      if (fa.Dsp) {
+        if (mom) hipLaunchKernelGGL((k_fit_taylor<true, true, WD>), g, b, lds, st, fa);
+        else hipLaunchKernelGGL((k_fit_taylor<false, true, WD>), g, b, lds, st, fa);
+      } else {
+        if (mom) hipLaunchKernelGGL((k_fit_taylor<true, false, WD>), g, b, lds, st, fa);
+        else hipLaunchKernelGGL((k_fit_taylor<false, false, WD>), g, b, lds, st, fa);
+      }
+    });
+  });
+}
+
+int stage_post(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const FitLaunch& L) {
+  return timed_on(ctx, PPF_K_POST, st, [&] {
+    WIDE_SWITCH(L.wide, {
+      hipLaunchKernelGGL((k_post<false, WD>), dim3(n), dim3(kBlock), L.lds_meta, st, fa);
+      hipLaunchKernelGGL((k_post<true, WD>), dim3(n), dim3(kBlock), L.lds_meta, st, fa);
+    });
+  });
+}
+
+// errs_out: the sigma each channel was fitted with (the data pass's), for
+// subints sa.sub0 .. of the batch
+int stage_errs(ppf_ctx* ctx, hipStream_t st, int n, const SpecArgs& sa, double* errs_out) {
+  if (!errs_out) return PPF_OK;
+  HIPCHK(ctx, hipMemcpyAsync(errs_out + (size_t)sa.sub0 * sa.nchan, sa.sig,
+                             (size_t)n * sa.nchan * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return PPF_OK;
+}
+
+// The trust-ncg scattering solve of nc subints with every evaluation split
+// over blocks: k_solve<true> with each evaluation over `cur` blocks per subint
+// (k_scat_sweep) and then every subint's solver step (k_scat_step).
+int scat_split_solve(ppf_ctx* ctx, const FitArgs& fa, int nc, int split, size_t lds_scat) {
+  const int nchan = fa.nchan;
+  double* part = static_cast<double*>(ctx->buf[kSpart].p);
+  int* ctrs = reinterpret_cast<int*>(part + (size_t)nc * ((nchan + 7) / 8) * kScatPart);
+  HIPCHK(ctx, hipMemsetAsync(ctrs, 0, 2 * sizeof(int), ctx->stream));
+  // iterations go in groups of kCheck launches; after each group its
+  // running count is copied to pinned memory, and the host reads group
+  // g's count only once group g + 1 is queued behind it, so the device
+  // never waits for the host (a group launched after the last subint has
+  // finished costs kCheck near-empty grids)
+  constexpr int kCheck = 4;
+  // once few subints are left (the tail of slow fits), each sweep is
+  // spread over more blocks: one 8-channel group per wave.  The group
+  // partials, and so every result, do not depend on the split.
+  int cur = split;
+  const int split_tail = std::max(split, std::min(32, (nchan + 31) / 32));
+  // groups after the first are one hipGraph launch each (the same kernels
+  // in the same order, captured once per call and split)
+  hipGraphExec_t gx[2] = {nullptr, nullptr};
+  auto graph_for = [&](int sp, hipGraphExec_t* ex) -> int {
+    if (*ex) return PPF_OK;
+    // captured on the context's second queue (the context stream may be
+    // the legacy default stream, which cannot capture); launched on the
+    // context stream
+    if (!ctx->stream2)
+      HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    hipStream_t cs = ctx->stream2;
+    hipGraph_t g = nullptr;
+    HIPCHK(ctx, hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    for (int k = 0; k < kCheck; ++k) {
+      hipLaunchKernelGGL(k_scat_sweep, dim3(nc, sp), dim3(kBlock), lds_scat, cs, fa, part, sp, 0);
+      hipLaunchKernelGGL(k_scat_step, dim3(nc), dim3(64), 0, cs, fa, part, 0, ctrs, k & 1);
+    }
+    HIPCHK(ctx, hipStreamEndCapture(cs, &g));
+    const hipError_t e = hipGraphInstantiate(ex, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess)
+      return fail(ctx, PPF_ERR_DEVICE, "scattering solve graph: %s", hipGetErrorString(e));
+    return PPF_OK;
+  };
+  // the execs are destroyed on every way out, error returns included, after
+  // the work launched from them has drained
+  struct GraphFree {
+    hipGraphExec_t* g;
+    hipStream_t st;
+    ~GraphFree() {
+      if (!g[0] && !g[1]) return;
+      (void)hipStreamSynchronize(st);
+      for (int i = 0; i < 2; ++i)
+        if (g[i]) (void)hipGraphExecDestroy(g[i]);
+    }
+  } gfree{gx, ctx->stream};
+  // group gi: iterations kCheck * gi ... + kCheck - 1 (the first is the
+  // init sweep); its count lands in active_h[gi & 1]
+  auto issue = [&](int gi) -> int {
+    const int it0 = kCheck * gi;
+    if (gi > 0 && ctx->opt[PPF_OPT_SCAT_GRAPH]) {
+      hipGraphExec_t* ex = &gx[cur == split ? 0 : 1];
+      if (int r = graph_for(cur, ex)) return r;
+      if (int r = timed(ctx, PPF_K_SOLVE, [&] { (void)hipGraphLaunch(*ex, ctx->stream); }))
+        return r;
+    } else {
+      for (int k = 0; k < kCheck; ++k) {
+        const int init = it0 + k == 0 ? 1 : 0;
+        if (int r = timed(ctx, PPF_K_SOLVE, [&] {
+              hipLaunchKernelGGL(k_scat_sweep, dim3(nc, cur), dim3(kBlock), lds_scat, ctx->stream,
+                                 fa, part, cur, init);
+            }))
+          return r;
+        if (int r = timed(ctx, PPF_K_SOLVE, [&] {
+              hipLaunchKernelGGL(k_scat_step, dim3(nc), dim3(64), 0, ctx->stream, fa, part, init,
+                                 ctrs, (it0 + k) & 1);
+            }))
+          return r;
+      }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->active_h + (gi & 1), ctrs + ((it0 + kCheck - 1) & 1),
+                               sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->scat_ev[gi & 1], ctx->stream));
+    return PPF_OK;
+  };
+  // trust-ncg stops a fit at 1000 iterations (+ the init sweep)
+  const int max_groups = (1001 + kCheck) / kCheck + 1;
+  if (int r = issue(0)) return r;
+  for (int gi = 0;; ++gi) {
+    if (gi + 1 < max_groups)
+      if (int r = issue(gi + 1)) return r;
+    HIPCHK(ctx, hipEventSynchronize(ctx->scat_ev[gi & 1]));
+    const int running = ctx->active_h[gi & 1];
+    if (running == 0 || gi + 1 >= max_groups) break;
+    if (running < ctx->opt[PPF_OPT_SCAT_TAIL]) cur = split_tail;
+  }
+  return PPF_OK;
+}
+
+bool fit_is_tnc(const ppf_fit_desc* d) {
+  return d->method == PPF_METHOD_TNC || d->method == PPF_METHOD_TNC_LEGACY;
+}
+// X, the cross-spectrum, is written once by the data pass.  Phase-family
+// subints are fitted from Taylor moments of it (k_fit_taylor); scattering
+// fits, and every fit under PPF_SOLVE_EXACT, sweep it directly.
+bool fit_is_exact(const ppf_fit_desc* d) { return (d->solver_flags & PPF_SOLVE_EXACT) != 0; }
+bool fit_is_taylor(const ppf_fit_desc* d) {
+  return !fit_is_exact(d) && d->method == PPF_METHOD_TRUST_NCG;
+}
+
+// The descriptor and result checks of ppf_fit_portrait_batch (nsub > 0);
+// *logN as check_nbin_any gives it.
+int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o, int* logN) {
+  if (d->nchan <= 0 || d->nchan > PPF_MAX_NCHAN)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d outside [1, %d]", d->nchan, PPF_MAX_NCHAN);
+  if (d->nmodel <= 0) return fail(ctx, PPF_ERR_INVALID, "nmodel must be >= 1");
+  if (d->method != PPF_METHOD_TRUST_NCG && !fit_is_tnc(d) && d->method != PPF_METHOD_NEWTON_CG)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "Method %d is not implemented.", d->method);
+  if (d->method == PPF_METHOD_TNC_LEGACY &&
+      !(d->fit_flags[0] && d->fit_flags[1] && !d->fit_flags[2] && !d->fit_flags[3] &&
+        !d->fit_flags[4]))
+    return fail(ctx, PPF_ERR_INVALID, "legacy TNC fits phase and DM only (fit_flags [1,1,0,0,0])");
+  if (d->solver_flags & ~(PPF_SOLVE_EXACT | PPF_SOLVE_EVAL | PPF_GUESS_DIRECT))
+    return fail(ctx, PPF_ERR_INVALID, "unknown solver_flags bits 0x%x", d->solver_flags);
+  if (!d->data || !d->model || !d->freqs || !d->P || !d->init || !d->nu_fit || !d->nu_out)
+    return fail(ctx, PPF_ERR_INVALID, "missing required input pointer");
+  if (!o->params || !o->param_errs || !o->nu_out || !o->cov || !o->scales || !o->scale_errs ||
+      !o->channel_snrs || !o->chi2 || !o->red_chi2 || !o->snr || !o->nfev || !o->status)
+    return fail(ctx, PPF_ERR_INVALID, "missing required output pointer");
+  if (d->guess && d->guess_Ns < 2) return fail(ctx, PPF_ERR_INVALID, "guess_Ns must be >= 2");
+  // nbin not a power of two: the generic-length data pass and template
+  // spectra (ppfit_generic.hip); every solver kernel takes any nbin
+  if (int r = check_nbin_any(ctx, d->nbin, logN)) return r;
+  // data-spectrum cache: sig, dsum and R live in the caller's arrays, and
+  // Taylor-path subints keep D instead of X (ppfit.h, PPF_SPEC_*)
+  const int smode = d->spec_mode;
+  if (smode != PPF_SPEC_NONE) {
+    if (smode != PPF_SPEC_STORE && smode != PPF_SPEC_USE)
+      return fail(ctx, PPF_ERR_INVALID, "spec_mode %d: PPF_SPEC_NONE, _STORE or _USE", smode);
+    if (!d->spec || !d->spec_sig || !d->spec_dsum || !d->spec_R)
+      return fail(ctx, PPF_ERR_INVALID, "spec_mode %d: spec, spec_sig, spec_dsum and spec_R "
+                  "are required", smode);
+    if (!fit_is_taylor(d) || d->fit_flags[3] || d->fit_flags[4])
+      return fail(ctx, PPF_ERR_UNSUPPORTED, "the data-spectrum cache takes phase-family "
+                  "trust-ncg fits only (tau and alpha not fitted, not PPF_SOLVE_EXACT)");
+  }
+  return PPF_OK;
+}
+
+// Everything of the two argument structs that comes from the descriptor, the
+// result struct and the context's settings (templates and tables:
+// fit_tables; workspace pointers: FitWorkspace::slice).
+void bind_fit_args(const ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o,
+                   SpecArgs& sa, FitArgs& fa) {
+  const int nbin = d->nbin;
+  sa.nchan = fa.nchan = d->nchan;
+  sa.NHP = fa.NHP = nharm_pad(nbin);
+  sa.kc = fa.kc = noise_kc(nbin);
+  sa.guess = fa.guess = d->guess;
+  sa.data = d->data;
+  sa.model_idx = fa.model_idx = d->model_idx;
+  sa.freqs = fa.freqs = d->freqs;
+  sa.errs = d->errs;
+  sa.mask = fa.mask = d->chan_mask;
+  sa.weights = d->weights;
+  sa.P = fa.P = d->P;
+  sa.init = fa.init = d->init;
+  sa.guess_nu = fa.guess_nu = d->guess_nu;
+  sa.log10_tau = fa.log10_tau = d->log10_tau;
+  sa.fit_tau = d->fit_flags[3] ? 1 : 0;
+  sa.exact = fit_is_exact(d) ? 1 : 0;
+  sa.spec_mode = d->spec_mode;
+
+  fa.nbin = nbin;
+  fa.NH = nbin / 2 + 1;
+  for (int i = 0; i < 5; ++i) fa.flags[i] = d->fit_flags[i] ? 1 : 0;
+  fa.option = d->option;
+  fa.is_toa = d->is_toa;
+  fa.Ns = d->guess_Ns;
+  fa.guess_wrap = d->guess_wrap;
+  fa.solver_flags = d->solver_flags;
+  fa.method = d->method;
+  fa.guess_wave = ctx->opt[PPF_OPT_GUESS_WAVE];
+  for (int i = 0; i < 5; ++i)
+    for (int j = 0; j < 2; ++j) fa.bounds[i][j] = d->bounds ? d->bounds[2 * i + j] : NAN;
+  fa.nu_fit = d->nu_fit;
+  fa.nu_out = d->nu_out;
+  fa.guess_tau = d->guess_tau;
+  fa.ptime = ctx->phase_prof ? static_cast<unsigned long long*>(ctx->buf[kPtime].p) : nullptr;
+  fa.trace = ctx->trace_cap > 0 ? ctx->trace : nullptr;
+  fa.trace_cap = ctx->trace_cap;
+  fa.o_params = o->params;
+  fa.o_param_errs = o->param_errs;
+  fa.o_nu_out = o->nu_out;
+  fa.o_cov = o->cov;
+  fa.o_scales = o->scales;
+  fa.o_scale_errs = o->scale_errs;
+  fa.o_channel_snrs = o->channel_snrs;
+  fa.o_chi2 = o->chi2;
+  fa.o_red_chi2 = o->red_chi2;
+  fa.o_snr = o->snr;
+  fa.o_nfev = o->nfev;
+  fa.o_status = o->status;
+  fa.o_init_used = o->init_used;
+  fa.o_fun = o->fun;
+  fa.o_cov_nosc = o->cov_nosc;
+  fa.o_grad = o->grad;
+  fa.o_hess = o->hess;
+}
+
+// Templates and tables of a fit call into the argument structs: twiddles,
+// template spectra, the mean template spectrum for the unmasked guess and
+// (Taylor path) the moment power table.
+int fit_tables(ppf_ctx* ctx, const ppf_fit_desc* d, SpecArgs& sa, FitArgs& fa) {
+  const int nchan = d->nchan, nbin = d->nbin, NHP = sa.NHP;
+  if (int r = twiddles(ctx, nbin, &fa.tw)) return r;
+  sa.tw = fa.tw;
+  double2* M;
+  double* pn;
+  double* M2;
+  if (int r = model_spectra(ctx, d->nmodel * nchan, nbin, d->model, 1, ctx->buf[kMspec], &M, &pn,
+                            &M2))
+    return r;
+  sa.M = fa.M = M;
+  fa.pn = pn;
+  fa.M2 = M2;
+  if (d->guess) {
+    if (int r = ensure(ctx, ctx->buf[kMmean], (size_t)d->nmodel * NHP * sizeof(double2))) return r;
+    double2* Mmean = reinterpret_cast<double2*>(ctx->buf[kMmean].p);
+    fa.Mmean = Mmean;
+    if (int r = timed(ctx, PPF_K_MODEL_FFT, [&] {
+          hipLaunchKernelGGL(k_model_mean, dim3((NHP + 255) / 256, d->nmodel), dim3(256), 0,
+                             ctx->stream, M, Mmean, nchan, NHP);
+        }))
+      return r;
+  }
+  if (fit_is_taylor(d))
+    if (int r = vpow_table(ctx, nbin, &fa.vpow)) return r;
+  return PPF_OK;
 }
 
 }  // namespace
@@ -392,19 +775,11 @@ void ppf_ctx_destroy(ppf_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream2);
     (void)hipStreamDestroy(ctx->stream2);
   }
-  for (auto p : ctx->tw) if (p) (void)hipFree(p);
-  for (auto p : ctx->vp) if (p) (void)hipFree(p);
-  for (auto& p : ctx->tw_gen) (void)hipFree(p.second);
-  for (auto& p : ctx->vp_gen) (void)hipFree(p.second);
-  if (ctx->ptime.p) (void)hipFree(ctx->ptime.p);
-  if (ctx->spart.p) (void)hipFree(ctx->spart.p);
-  if (ctx->tmpl.p) (void)hipFree(ctx->tmpl.p);
+  for (auto& p : ctx->tw) (void)hipFree(p.second);
+  for (auto& p : ctx->vp) (void)hipFree(p.second);
   if (ctx->active_h) (void)hipHostFree(ctx->active_h);
   for (auto e : ctx->scat_ev) if (e) (void)hipEventDestroy(e);
-  if (ctx->ws.p) (void)hipFree(ctx->ws.p);
-  if (ctx->mspec.p) (void)hipFree(ctx->mspec.p);
-  if (ctx->aux.p) (void)hipFree(ctx->aux.p);
-  if (ctx->mmean.p) (void)hipFree(ctx->mmean.p);
+  for (auto& b : ctx->buf) if (b.p) (void)hipFree(b.p);
   delete ctx;
 }
 
@@ -482,207 +857,36 @@ int ppf_reset_kernel_times(ppf_ctx* ctx) {
 int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o) {
   if (!ctx || !d || !o) return fail(ctx, PPF_ERR_INVALID, "null argument");
   if (d->nsub <= 0) return PPF_OK;
-  if (d->nchan <= 0 || d->nchan > PPF_MAX_NCHAN)
-    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d outside [1, %d]", d->nchan, PPF_MAX_NCHAN);
-  if (d->nmodel <= 0) return fail(ctx, PPF_ERR_INVALID, "nmodel must be >= 1");
-  const bool tnc = d->method == PPF_METHOD_TNC || d->method == PPF_METHOD_TNC_LEGACY;
-  const bool ncg = d->method == PPF_METHOD_NEWTON_CG;
-  if (d->method != PPF_METHOD_TRUST_NCG && !tnc && !ncg)
-    return fail(ctx, PPF_ERR_UNSUPPORTED, "Method %d is not implemented.", d->method);
-  if (d->method == PPF_METHOD_TNC_LEGACY &&
-      !(d->fit_flags[0] && d->fit_flags[1] && !d->fit_flags[2] && !d->fit_flags[3] &&
-        !d->fit_flags[4]))
-    return fail(ctx, PPF_ERR_INVALID, "legacy TNC fits phase and DM only (fit_flags [1,1,0,0,0])");
-  if (d->solver_flags & ~(PPF_SOLVE_EXACT | PPF_SOLVE_EVAL | PPF_GUESS_DIRECT))
-    return fail(ctx, PPF_ERR_INVALID, "unknown solver_flags bits 0x%x", d->solver_flags);
-  if (!d->data || !d->model || !d->freqs || !d->P || !d->init || !d->nu_fit || !d->nu_out)
-    return fail(ctx, PPF_ERR_INVALID, "missing required input pointer");
-  if (!o->params || !o->param_errs || !o->nu_out || !o->cov || !o->scales || !o->scale_errs ||
-      !o->channel_snrs || !o->chi2 || !o->red_chi2 || !o->snr || !o->nfev || !o->status)
-    return fail(ctx, PPF_ERR_INVALID, "missing required output pointer");
-  if (d->guess && d->guess_Ns < 2) return fail(ctx, PPF_ERR_INVALID, "guess_Ns must be >= 2");
-  int logN;
-  // nbin not a power of two: the generic-length data pass and template
-  // spectra (ppfit_generic.hip); every solver kernel takes any nbin
-  if (int r = check_nbin_any(ctx, d->nbin, &logN)) return r;
+  FitLaunch L;
+  if (int r = check_fit_desc(ctx, d, o, &L.logN)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const int nchan = d->nchan, nbin = d->nbin;
-  const int NH = nbin / 2 + 1, NHP = nharm_pad(nbin);
-  const int kc = noise_kc(nbin);
-  const double2* tw;
-  if (int r = twiddles(ctx, nbin, &tw)) return r;
-  double2* M;
-  double* pn;
-  double* M2;
-  if (int r = model_spectra(ctx, d->nmodel * nchan, nbin, d->model, 1, ctx->mspec, &M, &pn, &M2))
-    return r;
+  const int nchan = d->nchan, nbin = d->nbin, NH = nbin / 2 + 1;
+  const bool tnc = fit_is_tnc(d), ncg = d->method == PPF_METHOD_NEWTON_CG;
+  const bool exact = fit_is_exact(d), taylor = fit_is_taylor(d);
+  SpecArgs sa{};
+  FitArgs fa{};
+  bind_fit_args(ctx, d, o, sa, fa);
+  if (int r = fit_tables(ctx, d, sa, fa)) return r;
 
-  // X, the cross-spectrum, is written once by k_data_xspec.  Phase-family
-  // subints are fitted from Taylor moments of it (k_fit_taylor); scattering
-  // fits, and every fit under PPF_SOLVE_EXACT, sweep it directly.
-  const bool exact = (d->solver_flags & PPF_SOLVE_EXACT) != 0;
-  const bool taylor = !exact && d->method == PPF_METHOD_TRUST_NCG;
-  // data-spectrum cache: sig, dsum and R live in the caller's arrays, and
-  // Taylor-path subints keep D instead of X (ppfit.h, PPF_SPEC_*)
-  const int smode = d->spec_mode;
-  if (smode != PPF_SPEC_NONE) {
-    if (smode != PPF_SPEC_STORE && smode != PPF_SPEC_USE)
-      return fail(ctx, PPF_ERR_INVALID, "spec_mode %d: PPF_SPEC_NONE, _STORE or _USE", smode);
-    if (!d->spec || !d->spec_sig || !d->spec_dsum || !d->spec_R)
-      return fail(ctx, PPF_ERR_INVALID, "spec_mode %d: spec, spec_sig, spec_dsum and spec_R "
-                  "are required", smode);
-    if (!taylor || d->fit_flags[3] || d->fit_flags[4])
-      return fail(ctx, PPF_ERR_UNSUPPORTED, "the data-spectrum cache takes phase-family "
-                  "trust-ncg fits only (tau and alpha not fitted, not PPF_SOLVE_EXACT)");
-  }
-  // mean template spectrum for the unmasked guess
-  double2* Mmean = nullptr;
-  if (d->guess) {
-    if (int r = ensure(ctx, ctx->mmean, (size_t)d->nmodel * NHP * sizeof(double2))) return r;
-    Mmean = reinterpret_cast<double2*>(ctx->mmean.p);
-    if (int r = timed(ctx, PPF_K_MODEL_FFT, [&] {
-          hipLaunchKernelGGL(k_model_mean, dim3((NHP + 255) / 256, d->nmodel), dim3(256), 0,
-                             ctx->stream, M, Mmean, nchan, NHP);
-        }))
-      return r;
-  }
-
-  // per-subint workspace layout
-  const size_t bX = (size_t)nchan * NHP * sizeof(double2);
-  const size_t bT = taylor ? (size_t)2 * nchan * kMT * sizeof(double) : 0;
-  const size_t bR = (size_t)NHP * sizeof(double2);
-  const size_t bC = (size_t)nchan * sizeof(double);
-  const size_t bAcc = (size_t)2 * nchan * 10 * sizeof(double);
-  const size_t bW = (size_t)nchan * 8 * sizeof(double);
   // per-channel tables in HBM (the WIDE kernels, ppfit_kernels.hpp chan_tables)
   const bool wide = nchan > PPF_LDS_NCHAN || ctx->opt[PPF_OPT_HBM_TABLES] != 0;
-  const size_t bG = wide ? align256(std::max(align256((size_t)nchan * (5 * sizeof(double) +
-                                                                        sizeof(int))),
-                                             xspec_dyn_lds(nchan)))
-                         : 0;
-  const size_t per_sub = bX + bT + 2 * bR + 2 * bC + sizeof(SolveState) + bAcc + bW + bG;
-  int64_t chunk = ctx->ws_limit / (int64_t)(per_sub + 1024);
-  if (chunk < 1) chunk = 1;
-  if (chunk > d->nsub) chunk = d->nsub;
-  const size_t cs = (size_t)chunk;
-  const size_t offX = 0;
-  const size_t offR = align256(offX + cs * bX);
-  const size_t offMm = align256(offR + cs * bR);
-  const size_t offSig = align256(offMm + cs * bR);
-  const size_t offDs = align256(offSig + cs * bC);
-  const size_t offSt = align256(offDs + cs * bC);
-  const size_t offAcc = align256(offSt + cs * sizeof(SolveState));
-  const size_t offW = align256(offAcc + cs * bAcc);
-  const size_t offT = align256(offW + cs * bW);
-  const size_t offG = align256(offT + cs * bT);
-  const size_t total = align256(offG + cs * bG);
-  if (int r = ensure(ctx, ctx->ws, total)) return r;
-  char* base = static_cast<char*>(ctx->ws.p);
+  FitWorkspace ws(nchan, fa.NHP, taylor, wide, ctx->ws_limit, d->nsub);
+  if (int r = ensure(ctx, ctx->buf[kWs], ws.total)) return r;
+  ws.base = static_cast<char*>(ctx->buf[kWs].p);
+  ws.slice(0, sa, fa);
+  const int64_t chunk = ws.chunk;
 
-  SpecArgs sa;
-  sa.nchan = nchan;
-  sa.NHP = NHP;
-  sa.kc = kc;
-  sa.guess = d->guess;
-  sa.data = d->data;
-  sa.M = M;
-  sa.model_idx = d->model_idx;
-  sa.freqs = d->freqs;
-  sa.errs = d->errs;
-  sa.mask = d->chan_mask;
-  sa.weights = d->weights;
-  sa.P = d->P;
-  sa.init = d->init;
-  sa.guess_nu = d->guess_nu;
-  sa.log10_tau = d->log10_tau;
-  sa.fit_tau = d->fit_flags[3] ? 1 : 0;
-  sa.exact = exact ? 1 : 0;
-  sa.spec_mode = smode;
-  sa.D = nullptr;
-  sa.X = reinterpret_cast<double2*>(base + offX);
-  sa.R = reinterpret_cast<double2*>(base + offR);
-  sa.sig = reinterpret_cast<double*>(base + offSig);
-  sa.dsum = reinterpret_cast<double*>(base + offDs);
-  sa.tw = tw;
-  sa.gdyn = wide ? reinterpret_cast<unsigned char*>(base + offG) : nullptr;
-  sa.gdyn_stride = bG;
-
-  FitArgs fa{};
-  fa.nchan = nchan;
-  fa.nbin = nbin;
-  fa.NH = NH;
-  fa.NHP = NHP;
-  fa.kc = kc;
-  for (int i = 0; i < 5; ++i) fa.flags[i] = d->fit_flags[i] ? 1 : 0;
-  fa.log10_tau = d->log10_tau;
-  fa.option = d->option;
-  fa.is_toa = d->is_toa;
-  fa.guess = d->guess;
-  fa.Ns = d->guess_Ns;
-  fa.guess_wrap = d->guess_wrap;
-  fa.solver_flags = d->solver_flags;
-  fa.method = d->method;
-  fa.guess_wave = ctx->opt[PPF_OPT_GUESS_WAVE];
-  for (int i = 0; i < 5; ++i)
-    for (int j = 0; j < 2; ++j) fa.bounds[i][j] = d->bounds ? d->bounds[2 * i + j] : NAN;
-  fa.X = sa.X;
-  fa.Dsp = nullptr;
-  fa.R = sa.R;
-  fa.M = M;
-  fa.M2 = M2;
-  fa.pn = pn;
-  fa.model_idx = d->model_idx;
-  fa.sig = sa.sig;
-  fa.dsum = sa.dsum;
-  fa.freqs = d->freqs;
-  fa.mask = d->chan_mask;
-  fa.P = d->P;
-  fa.init = d->init;
-  fa.nu_fit = d->nu_fit;
-  fa.nu_out = d->nu_out;
-  fa.guess_nu = d->guess_nu;
-  fa.guess_tau = d->guess_tau;
-  fa.st = reinterpret_cast<SolveState*>(base + offSt);
-  fa.acc = reinterpret_cast<double*>(base + offAcc);
-  fa.wsc = reinterpret_cast<double*>(base + offW);
-  fa.gdyn = sa.gdyn;
-  fa.gdyn_stride = bG;
-  fa.T = taylor ? reinterpret_cast<double*>(base + offT) : nullptr;
-  fa.tw = tw;
-  fa.vpow = nullptr;
-  if (taylor)
-    if (int r = vpow_table(ctx, nbin, &fa.vpow)) return r;
-  fa.Mmean = Mmean;
-  fa.ptime = ctx->phase_prof ? static_cast<unsigned long long*>(ctx->ptime.p) : nullptr;
-  fa.trace = ctx->trace_cap > 0 ? ctx->trace : nullptr;
-  fa.trace_cap = ctx->trace_cap;
-  fa.o_params = o->params;
-  fa.o_param_errs = o->param_errs;
-  fa.o_nu_out = o->nu_out;
-  fa.o_cov = o->cov;
-  fa.o_scales = o->scales;
-  fa.o_scale_errs = o->scale_errs;
-  fa.o_channel_snrs = o->channel_snrs;
-  fa.o_chi2 = o->chi2;
-  fa.o_red_chi2 = o->red_chi2;
-  fa.o_snr = o->snr;
-  fa.o_nfev = o->nfev;
-  fa.o_status = o->status;
-  fa.o_init_used = o->init_used;
-  fa.o_fun = o->fun;
-  fa.o_cov_nosc = o->cov_nosc;
-  fa.o_grad = o->grad;
-  fa.o_hess = o->hess;
-
-  // dynamic LDS of the Meta kernels (none for the WIDE ones)
-  const size_t lds_meta =
-      wide ? 0 : align256((size_t)nchan * (5 * sizeof(double) + sizeof(int)));
-  const size_t lds_xspec = wide ? 0 : xspec_dyn_lds(nchan);
+  L.nbin = nbin;
+  L.wide = wide;
+  L.lds_meta = wide ? 0 : meta_lds(nchan);
+  L.lds_xspec = wide ? 0 : xspec_dyn_lds(nchan);
   // k_fit_taylor keeps moments [0, tnl) of T slot 0 in LDS (all of them when
   // they fit beside kTaylorBlocksPerCU - 1 other blocks; none when WIDE)
-  fa.tnl = taylor && !wide ? taylor_lds_moments(nchan, lds_meta) : 0;
-  fa.tlds = fa.tnl > 0 ? (int)lds_meta : 0;
-  const size_t lds_taylor = lds_meta + (size_t)nchan * fa.tnl * sizeof(double);
+  fa.tnl = taylor && !wide ? taylor_lds_moments(ctx, nchan, L.lds_meta) : 0;
+  fa.tlds = fa.tnl > 0 ? (int)L.lds_meta : 0;
+  L.lds_taylor = L.lds_meta + (size_t)nchan * fa.tnl * sizeof(double);
+  L.lds_guess =
+      (size_t)(fa.NHP + (d->guess ? pfa_scratch_slots(d->guess_Ns, NH) : 0)) * sizeof(double2);
   // trust-ncg scattering fits: every evaluation split over blocks of >= 64
   // fitted channels (k_scat_sweep / k_scat_step)
   // (PPF_OPT_SCAT_SPLIT = 0: one block per subint, k_solve<true>)
@@ -690,9 +894,9 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
                           d->method == PPF_METHOD_TRUST_NCG && !wide;
   const int split = std::max(1, std::min(16, nchan / 64));
   // the two-phase sweep's rows (any block's channel range at split or more)
-  const size_t lds_scat = PPF_SCAT_TWO_PHASE ? scat_sweep_lds(nchan, split) : lds_meta;
+  L.lds_scat = PPF_SCAT_TWO_PHASE ? scat_sweep_lds(nchan, split) : L.lds_meta;
   if (split_scat) {
-    if (int r = ensure(ctx, ctx->spart,
+    if (int r = ensure(ctx, ctx->buf[kSpart],
                        (size_t)chunk * ((nchan + 7) / 8) * kScatPart * sizeof(double) +
                            64 * sizeof(int) + 256))
       return r;
@@ -700,19 +904,17 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
     for (auto& e : ctx->scat_ev)
       if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  const size_t lds_guess =
-      (size_t)(NHP + (d->guess ? pfa_scratch_slots(d->guess_Ns, NH) : 0)) * sizeof(double2);
   // the cache rows of subints sub .. (spec_mode set): D, and sig / dsum / R in
   // place of the workspace's
   auto bind_spec = [&](SpecArgs& sp, FitArgs& fp, int64_t sub) {
-    if (smode == PPF_SPEC_NONE) return;
-    sp.D = reinterpret_cast<double2*>(d->spec) + (size_t)sub * nchan * NHP;
+    if (d->spec_mode == PPF_SPEC_NONE) return;
+    sp.D = reinterpret_cast<double2*>(d->spec) + (size_t)sub * nchan * fa.NHP;
     fp.Dsp = sp.D;
     sp.sig = d->spec_sig + (size_t)sub * nchan;
     fp.sig = sp.sig;
     sp.dsum = d->spec_dsum + (size_t)sub * nchan;
     fp.dsum = sp.dsum;
-    sp.R = reinterpret_cast<double2*>(d->spec_R) + (size_t)sub * NHP;
+    sp.R = reinterpret_cast<double2*>(d->spec_R) + (size_t)sub * fa.NHP;
     fp.R = sp.R;
   };
   // Phase-family Taylor path, several pieces per chunk on two queues: piece
@@ -739,68 +941,25 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
         SpecArgs sp = sa;
         FitArgs fp = fa;
         sp.sub0 = fp.sub0 = (int)s0 + off;
-        sp.X = sa.X + (size_t)off * nchan * NHP;
-        fp.X = sp.X;
-        sp.R = sa.R + (size_t)off * NHP;
-        fp.R = sp.R;
-        sp.sig = sa.sig + (size_t)off * nchan;
-        fp.sig = sp.sig;
-        sp.dsum = sa.dsum + (size_t)off * nchan;
-        fp.dsum = sp.dsum;
-        fp.st = fa.st + off;
-        fp.T = fa.T + (size_t)off * 2 * nchan * kMT;
-        fp.acc = fa.acc + (size_t)off * 2 * nchan * 10;
-        fp.wsc = fa.wsc + (size_t)off * nchan * 8;
-        if (wide) {
-          sp.gdyn = sa.gdyn + (size_t)off * bG;
-          fp.gdyn = sp.gdyn;
-        }
+        ws.slice(off, sp, fp);
         bind_spec(sp, fp, s0 + off);
         if (prev_x) HIPCHK(ctx, hipStreamWaitEvent(st, prev_x, 0));
-        if (int r = timed_on(ctx, PPF_K_DATA_XSPEC, st, [&] {
-              if (logN < 0) launch_data_gen(sp, n, nbin, st);
-              LOGN_SWITCH(logN, WIDE_SWITCH(wide, hipLaunchKernelGGL((k_data_xspec<LG, WD>), dim3(n),
-                                                   dim3(XspecCfg<LG>::WPB * 64),
-                                                   lds_xspec, st, sp)));
-            }))
-          return r;
+        if (int r = stage_data(ctx, st, n, sp, L)) return r;
         if (int r = sync_event(ctx, ev++, &prev_x)) return r;
         HIPCHK(ctx, hipEventRecord(prev_x, st));
-        if (int r = timed_on(ctx, PPF_K_GUESS, st, [&] {
-              if (d->guess && fp.guess_wave)
-                hipLaunchKernelGGL(k_guess_w, dim3(n), dim3(64), 0, st, fp);
-              hipLaunchKernelGGL(k_guess, dim3(n), dim3(kBlock), d->guess ? lds_guess : 0, st, fp);
-            }))
-          return r;
-        if (!ctx->opt[PPF_OPT_FUSE_MOMENTS])
-          if (int r = timed_on(ctx, PPF_K_MOMENTS, st, [&] {
-                const dim3 g(n, (nchan + 16 * kWaves - 1) / (16 * kWaves));
-                launch_moments(g, st, fp);
-              }))
-            return r;
-        if (int r = timed_on(ctx, PPF_K_FIT_TAYLOR, st, [&] {
-              launch_fit_taylor(ctx, dim3(n), lds_taylor, st, fp);
-            }))
-          return r;
+        if (int r = stage_guess(ctx, st, n, fp, L)) return r;
+        if (int r = stage_moments(ctx, st, n, fp)) return r;
+        if (int r = stage_taylor(ctx, st, n, fp, L)) return r;
         // subints the Taylor path does not take (tau != 0 at the start, not
         // fitted): the one-workgroup scattering solve and post-fit, as on
         // one queue (both exit at once for every other subint)
         if (int r = timed_on(ctx, PPF_K_SOLVE, st, [&] {
               WIDE_SWITCH(wide, hipLaunchKernelGGL((k_solve<true, WD>), dim3(n), dim3(kBlock),
-                                                   lds_meta, st, fp));
+                                                   L.lds_meta, st, fp));
             }))
           return r;
-        if (int r = timed_on(ctx, PPF_K_POST, st, [&] {
-              WIDE_SWITCH(wide, {
-                hipLaunchKernelGGL((k_post<false, WD>), dim3(n), dim3(kBlock), lds_meta, st, fp);
-                hipLaunchKernelGGL((k_post<true, WD>), dim3(n), dim3(kBlock), lds_meta, st, fp);
-              });
-            }))
-          return r;
-        if (o->errs_out)
-          HIPCHK(ctx, hipMemcpyAsync(o->errs_out + (size_t)(s0 + off) * nchan, sp.sig,
-                                     (size_t)n * nchan * sizeof(double),
-                                     hipMemcpyDeviceToDevice, st));
+        if (int r = stage_post(ctx, st, n, fp, L)) return r;
+        if (int r = stage_errs(ctx, st, n, sp, o->errs_out)) return r;
       }
     }
     // join: the caller's stream sees every piece
@@ -810,174 +969,43 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, done, 0));
     return PPF_OK;
   }
+  // One queue, the whole chunk at a time.
+  hipStream_t st = ctx->stream;
   for (int64_t s0 = 0; s0 < d->nsub; s0 += chunk) {
     const int nc = (int)std::min<int64_t>(chunk, d->nsub - s0);
-    sa.sub0 = (int)s0;
-    fa.sub0 = (int)s0;
+    sa.sub0 = fa.sub0 = (int)s0;
     bind_spec(sa, fa, s0);
-    if (int r = timed(ctx, PPF_K_DATA_XSPEC, [&] {
-          if (logN < 0) launch_data_gen(sa, nc, nbin, ctx->stream);
-          LOGN_SWITCH(logN, WIDE_SWITCH(wide, hipLaunchKernelGGL((k_data_xspec<LG, WD>), dim3(nc),
-                                                                 dim3(XspecCfg<LG>::WPB * 64),
-                                                                 lds_xspec, ctx->stream, sa)));
-        }))
-      return r;
-    if (int r = timed(ctx, PPF_K_GUESS, [&] {
-          if (d->guess && fa.guess_wave)
-            hipLaunchKernelGGL(k_guess_w, dim3(nc), dim3(64), 0, ctx->stream, fa);
-          hipLaunchKernelGGL(k_guess, dim3(nc), dim3(kBlock), d->guess ? lds_guess : 0,
-                             ctx->stream, fa);
-        }))
-      return r;
+    if (int r = stage_data(ctx, st, nc, sa, L)) return r;
+    if (int r = stage_guess(ctx, st, nc, fa, L)) return r;
     // each subint runs in exactly one of the exact phase-only / scattering /
     // fused Taylor variants (the others exit at once)
     if (int r = timed(ctx, PPF_K_SOLVE, [&] {
+          const dim3 g(nc), b(kBlock);
+          const size_t lds = L.lds_meta;
           WIDE_SWITCH(wide, {
             if (tnc) {
-              hipLaunchKernelGGL((k_tnc<false, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                                 fa);
-              hipLaunchKernelGGL((k_tnc<true, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                                 fa);
+              hipLaunchKernelGGL((k_tnc<false, WD>), g, b, lds, st, fa);
+              hipLaunchKernelGGL((k_tnc<true, WD>), g, b, lds, st, fa);
               return;
             }
             if (ncg) {
-              hipLaunchKernelGGL((k_ncg<false, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                                 fa);
-              hipLaunchKernelGGL((k_ncg<true, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                                 fa);
+              hipLaunchKernelGGL((k_ncg<false, WD>), g, b, lds, st, fa);
+              hipLaunchKernelGGL((k_ncg<true, WD>), g, b, lds, st, fa);
               return;
             }
-            if (exact)
-              hipLaunchKernelGGL((k_solve<false, WD>), dim3(nc), dim3(kBlock), lds_meta,
-                                 ctx->stream, fa);
-            if (!split_scat)
-              hipLaunchKernelGGL((k_solve<true, WD>), dim3(nc), dim3(kBlock), lds_meta,
-                                 ctx->stream, fa);
+            if (exact) hipLaunchKernelGGL((k_solve<false, WD>), g, b, lds, st, fa);
+            if (!split_scat) hipLaunchKernelGGL((k_solve<true, WD>), g, b, lds, st, fa);
           });
         }))
       return r;
-    if (split_scat && !tnc && !ncg) {
-      // k_solve<true> with each evaluation over `cur` blocks per subint
-      // (k_scat_sweep) and then every subint's solver step (k_scat_step)
-      double* part = static_cast<double*>(ctx->spart.p);
-      int* ctrs = reinterpret_cast<int*>(part + (size_t)nc * ((nchan + 7) / 8) * kScatPart);
-      HIPCHK(ctx, hipMemsetAsync(ctrs, 0, 2 * sizeof(int), ctx->stream));
-      // iterations go in groups of kCheck launches; after each group its
-      // running count is copied to pinned memory, and the host reads group
-      // g's count only once group g + 1 is queued behind it, so the device
-      // never waits for the host (a group launched after the last subint has
-      // finished costs kCheck near-empty grids)
-      constexpr int kCheck = 4;
-      // once few subints are left (the tail of slow fits), each sweep is
-      // spread over more blocks: one 8-channel group per wave.  The group
-      // partials, and so every result, do not depend on the split.
-      int cur = split;
-      const int split_tail = std::max(split, std::min(32, (nchan + 31) / 32));
-      // groups after the first are one hipGraph launch each (the same kernels
-      // in the same order, captured once per call and split)
-      hipGraphExec_t gx[2] = {nullptr, nullptr};
-      auto graph_for = [&](int sp, hipGraphExec_t* ex) -> int {
-        if (*ex) return PPF_OK;
-        // captured on the context's second queue (the context stream may be
-        // the legacy default stream, which cannot capture); launched on the
-        // context stream
-        if (!ctx->stream2)
-          HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-        hipStream_t cs = ctx->stream2;
-        hipGraph_t g = nullptr;
-        HIPCHK(ctx, hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        for (int k = 0; k < kCheck; ++k) {
-          hipLaunchKernelGGL(k_scat_sweep, dim3(nc, sp), dim3(kBlock), lds_scat, cs, fa, part, sp,
-                             0);
-          hipLaunchKernelGGL(k_scat_step, dim3(nc), dim3(64), 0, cs, fa, part, 0, ctrs, k & 1);
-        }
-        HIPCHK(ctx, hipStreamEndCapture(cs, &g));
-        const hipError_t e = hipGraphInstantiate(ex, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess)
-          return fail(ctx, PPF_ERR_DEVICE, "scattering solve graph: %s", hipGetErrorString(e));
-        return PPF_OK;
-      };
-      // the execs are destroyed on every way out of the loop, error returns
-      // included, after the work launched from them has drained
-      struct GraphFree {
-        hipGraphExec_t* g;
-        hipStream_t st;
-        ~GraphFree() {
-          if (!g[0] && !g[1]) return;
-          (void)hipStreamSynchronize(st);
-          for (int i = 0; i < 2; ++i)
-            if (g[i]) (void)hipGraphExecDestroy(g[i]);
-        }
-      } gfree{gx, ctx->stream};
-      // group gi: iterations kCheck * gi ... + kCheck - 1 (the first is the
-      // init sweep); its count lands in active_h[gi & 1]
-      auto issue = [&](int gi) -> int {
-        const int it0 = kCheck * gi;
-        if (gi > 0 && ctx->opt[PPF_OPT_SCAT_GRAPH]) {
-          hipGraphExec_t* ex = &gx[cur == split ? 0 : 1];
-          if (int r = graph_for(cur, ex)) return r;
-          if (int r = timed(ctx, PPF_K_SOLVE, [&] { (void)hipGraphLaunch(*ex, ctx->stream); }))
-            return r;
-        } else {
-          for (int k = 0; k < kCheck; ++k) {
-            const int init = it0 + k == 0 ? 1 : 0;
-            if (int r = timed(ctx, PPF_K_SOLVE, [&] {
-                  hipLaunchKernelGGL(k_scat_sweep, dim3(nc, cur), dim3(kBlock), lds_scat,
-                                     ctx->stream, fa, part, cur, init);
-                }))
-              return r;
-            if (int r = timed(ctx, PPF_K_SOLVE, [&] {
-                  hipLaunchKernelGGL(k_scat_step, dim3(nc), dim3(64), 0, ctx->stream, fa, part,
-                                     init, ctrs, (it0 + k) & 1);
-                }))
-              return r;
-          }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->active_h + (gi & 1), ctrs + ((it0 + kCheck - 1) & 1),
-                                   sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(ctx->scat_ev[gi & 1], ctx->stream));
-        return PPF_OK;
-      };
-      // trust-ncg stops a fit at 1000 iterations (+ the init sweep)
-      const int max_groups = (1001 + kCheck) / kCheck + 1;
-      if (int r = issue(0)) return r;
-      for (int gi = 0;; ++gi) {
-        if (gi + 1 < max_groups)
-          if (int r = issue(gi + 1)) return r;
-        HIPCHK(ctx, hipEventSynchronize(ctx->scat_ev[gi & 1]));
-        const int running = ctx->active_h[gi & 1];
-        if (running == 0 || gi + 1 >= max_groups) break;
-        if (running < ctx->opt[PPF_OPT_SCAT_TAIL]) cur = split_tail;
-      }
-    }
+    if (split_scat && !tnc && !ncg)
+      if (int r = scat_split_solve(ctx, fa, nc, split, L.lds_scat)) return r;
     if (taylor) {
-      // the first moment pass inside k_fit_taylor (default), or its own
-      // launch (PPF_OPT_FUSE_MOMENTS = 0)
-      if (!ctx->opt[PPF_OPT_FUSE_MOMENTS])
-        if (int r = timed(ctx, PPF_K_MOMENTS, [&] {
-              const dim3 g(nc, (nchan + 16 * kWaves - 1) / (16 * kWaves));
-              launch_moments(g, ctx->stream, fa);
-            }))
-          return r;
-      if (int r = timed(ctx, PPF_K_FIT_TAYLOR, [&] {
-            launch_fit_taylor(ctx, dim3(nc), lds_taylor, ctx->stream, fa);
-          }))
-        return r;
+      if (int r = stage_moments(ctx, st, nc, fa)) return r;
+      if (int r = stage_taylor(ctx, st, nc, fa, L)) return r;
     }
-    if (int r = timed(ctx, PPF_K_POST, [&] {
-          WIDE_SWITCH(wide, {
-            hipLaunchKernelGGL((k_post<false, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                               fa);
-            hipLaunchKernelGGL((k_post<true, WD>), dim3(nc), dim3(kBlock), lds_meta, ctx->stream,
-                               fa);
-          });
-        }))
-      return r;
-    if (o->errs_out)  // the sigma each channel was fitted with (k_data_xspec)
-      HIPCHK(ctx, hipMemcpyAsync(o->errs_out + (size_t)s0 * nchan, sa.sig,
-                                 (size_t)nc * nchan * sizeof(double), hipMemcpyDeviceToDevice,
-                                 ctx->stream));
+    if (int r = stage_post(ctx, st, nc, fa, L)) return r;
+    if (int r = stage_errs(ctx, st, nc, sa, o->errs_out)) return r;
   }
   return PPF_OK;
 }
@@ -986,12 +1014,12 @@ int ppf_phase_profile(ppf_ctx* ctx, int32_t enable, uint64_t* out) {
   if (!ctx) return fail(ctx, PPF_ERR_INVALID, "null context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t bytes = PPF_PHASE_N * sizeof(uint64_t);
-  if (!ctx->ptime.p) {
-    if (int r = ensure(ctx, ctx->ptime, bytes)) return r;
-    HIPCHK(ctx, hipMemsetAsync(ctx->ptime.p, 0, bytes, ctx->stream));
+  if (!ctx->buf[kPtime].p) {
+    if (int r = ensure(ctx, ctx->buf[kPtime], bytes)) return r;
+    HIPCHK(ctx, hipMemsetAsync(ctx->buf[kPtime].p, 0, bytes, ctx->stream));
   }
-  if (out) HIPCHK(ctx, hipMemcpyAsync(out, ctx->ptime.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->ptime.p, 0, bytes, ctx->stream));
+  if (out) HIPCHK(ctx, hipMemcpyAsync(out, ctx->buf[kPtime].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->buf[kPtime].p, 0, bytes, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->phase_prof = enable != 0;
   return PPF_OK;
@@ -1036,7 +1064,7 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const doubl
   }
   double2* M;
   double* pn;
-  if (int r = model_spectra(ctx, nmodel, nbin, model, 1, ctx->aux, &M, &pn)) return r;
+  if (int r = model_spectra(ctx, nmodel, nbin, model, 1, ctx->buf[kAux], &M, &pn)) return r;
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   PhaseShiftArgs pa;
@@ -1070,11 +1098,7 @@ int ppf_rotate_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   return timed(ctx, PPF_K_ROTATE, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_rotate_rows_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin),
-                         ctx->stream, in, phase, nullptr, out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rotate_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, in, phase, nullptr, out, tw));
+    launch_rotate_rows(ctx->stream, logN, nbin, nrow, in, phase, nullptr, out, tw);
   });
 }
 
@@ -1089,11 +1113,7 @@ int ppf_scatter_rotate_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const doub
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   if (!phase) return fail(ctx, PPF_ERR_INVALID, "phase must be given (zeros for none)");
   return timed(ctx, PPF_K_ROTATE, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_rotate_rows_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin),
-                         ctx->stream, in, phase, tau, out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rotate_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, in, phase, tau, out, tw));
+    launch_rotate_rows(ctx->stream, logN, nbin, nrow, in, phase, tau, out, tw);
   });
 }
 
@@ -1129,8 +1149,8 @@ int ppf_spline_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin_in, int32_t nb
   const size_t nrows_in = resample ? (size_t)nrow * nbin_in : 0;
   const size_t hin = (size_t)nbin_in / 2 + 1, hout = (size_t)nbin / 2 + 1;
   const size_t nspec = resample ? (size_t)nrow * (hin + hout) * 2 : 0;
-  if (int r = ensure(ctx, ctx->tmpl, (ntc + nrows_in + nspec) * sizeof(double))) return r;
-  double* base = static_cast<double*>(ctx->tmpl.p);
+  if (int r = ensure(ctx, ctx->buf[kTmpl], (ntc + nrows_in + nspec) * sizeof(double))) return r;
+  double* base = static_cast<double*>(ctx->buf[kTmpl].p);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // tmpl may still feed an earlier launch
   SplineArgs s;
   s.nbin = nbin_in;
@@ -1162,18 +1182,10 @@ int ppf_spline_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin_in, int32_t nb
   const double shift = 0.5 * (1.0 / (double)nbin - 1.0 / (double)nbin_in);
   const size_t ny = (size_t)nrow * hout;
   return timed(ctx, PPF_K_MODEL_FFT, [&] {
-    if (logI < 0)
-      hipLaunchKernelGGL(k_rfft_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin_in),
-                         ctx->stream, rows, X, twi, nbin_in);
-    LOGN_SWITCH(logI, hipLaunchKernelGGL(k_rfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, ctx->stream,
-                                         rows, X, twi));
+    launch_rfft_rows(ctx->stream, logI, nbin_in, nrow, rows, X, twi);
     hipLaunchKernelGGL(k_resample_spec, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0,
                        ctx->stream, X, nbin_in, nbin, shift, nrow, Y);
-    if (logO < 0)
-      hipLaunchKernelGGL(k_irfft_rows_gen, dim3(nrow), dim3(kBlock), hout * sizeof(double2),
-                         ctx->stream, Y, out, two, nbin);
-    LOGN_SWITCH(logO, hipLaunchKernelGGL(k_irfft_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, Y, out, two));
+    launch_irfft_rows(ctx->stream, logO, nbin, nrow, Y, out, two);
   });
 }
 
@@ -1218,23 +1230,15 @@ int ppf_instrumental_response_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, con
       hipLaunchKernelGGL(k_ir_spec, dim3(grid), dim3(256), 0, ctx->stream, nullptr, out, nrow,
                          (int)nh, g, freqs);
     });
-  if (int r = ensure(ctx, ctx->tmpl, n * sizeof(double2))) return r;
-  double2* X = static_cast<double2*>(ctx->tmpl.p);
+  if (int r = ensure(ctx, ctx->buf[kTmpl], n * sizeof(double2))) return r;
+  double2* X = static_cast<double2*>(ctx->buf[kTmpl].p);
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   return timed(ctx, PPF_K_MODEL_FFT, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_rfft_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin),
-                         ctx->stream, in, X, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, ctx->stream,
-                                         in, X, tw));
+    launch_rfft_rows(ctx->stream, logN, nbin, nrow, in, X, tw);
     hipLaunchKernelGGL(k_ir_spec, dim3(grid), dim3(256), 0, ctx->stream, X, nullptr, nrow, (int)nh,
                        g, freqs);
-    if (logN < 0)
-      hipLaunchKernelGGL(k_irfft_rows_gen, dim3(nrow), dim3(kBlock), nh * sizeof(double2),
-                         ctx->stream, X, out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_irfft_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, X, out, tw));
+    launch_irfft_rows(ctx->stream, logN, nbin, nrow, X, out, tw);
   });
 }
 
@@ -1261,11 +1265,7 @@ int ppf_irfft_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* spec,
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   const double2* sp = reinterpret_cast<const double2*>(spec);
   return timed(ctx, PPF_K_IRFFT, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_irfft_rows_gen, dim3(nrow), dim3(kBlock),
-                         (size_t)(nbin / 2 + 1) * sizeof(double2), ctx->stream, sp, out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_irfft_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, sp, out, tw));
+    launch_irfft_rows(ctx->stream, logN, nbin, nrow, sp, out, tw);
   });
 }
 
@@ -1297,7 +1297,7 @@ int ppf_synth_portraits(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
   HIPCHK(ctx, hipSetDevice(ctx->device));
   double2* M;
   double* pn;
-  if (int r = model_spectra(ctx, nchan, nbin, model, 0, ctx->aux, &M, &pn)) return r;
+  if (int r = model_spectra(ctx, nchan, nbin, model, 0, ctx->buf[kAux], &M, &pn)) return r;
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   const int NHP = nharm_pad(nbin);
@@ -1305,9 +1305,8 @@ int ppf_synth_portraits(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
   if (rows > 0x7fffffff) return fail(ctx, PPF_ERR_INVALID, "too many rows");
   return timed(ctx, PPF_K_SYNTH, [&] {
     if (logN < 0)
-      hipLaunchKernelGGL(k_synth_gen, dim3((unsigned)rows), dim3(kBlock),
-                         (size_t)(nbin / 2 + 1) * sizeof(double2), ctx->stream, M, phase, data,
-                         nchan, NHP, sigma, seed, sub0, tw, nbin);
+      hipLaunchKernelGGL(k_synth_gen, dim3((unsigned)rows), dim3(kBlock), gen_spec_lds(nbin),
+                         ctx->stream, M, phase, data, nchan, NHP, sigma, seed, sub0, tw, nbin);
     LOGN_SWITCH(logN, hipLaunchKernelGGL(k_synth<LG>, dim3((unsigned)rows), dim3(kBlock), 0,
                                          ctx->stream, M, phase, data, nchan, NHP, sigma, seed,
                                          sub0, tw));
@@ -1335,8 +1334,8 @@ int ppf_rotate_accumulate(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbi
   if (nsplit > nsub) nsplit = nsub;
   if (nsplit < 1) nsplit = 1;
   const size_t count = (size_t)nchan * NH;
-  if (int r = ensure(ctx, ctx->aux, (size_t)nsplit * count * sizeof(double2))) return r;
-  double2* partial = reinterpret_cast<double2*>(ctx->aux.p);
+  if (int r = ensure(ctx, ctx->buf[kAux], (size_t)nsplit * count * sizeof(double2))) return r;
+  double2* partial = reinterpret_cast<double2*>(ctx->buf[kAux].p);
   if (int r = timed(ctx, PPF_K_ROT_ACCUM, [&] {
         if (logN < 0)
           hipLaunchKernelGGL(k_rot_accum_gen, dim3(nsplit * nchan), dim3(kBlock),
@@ -1379,8 +1378,8 @@ int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_
   if (nsplit > nsub) nsplit = nsub;
   if (nsplit < 1) nsplit = 1;
   const size_t count = (size_t)nchan * NH;
-  if (int r = ensure(ctx, ctx->aux, (size_t)nsplit * count * sizeof(double2))) return r;
-  double2* partial = reinterpret_cast<double2*>(ctx->aux.p);
+  if (int r = ensure(ctx, ctx->buf[kAux], (size_t)nsplit * count * sizeof(double2))) return r;
+  double2* partial = reinterpret_cast<double2*>(ctx->buf[kAux].p);
   if (int r = timed(ctx, PPF_K_ROT_ACCUM, [&] {
         hipLaunchKernelGGL(k_rot_accum_spec, dim3(nsplit * nchan), dim3(256), 0, ctx->stream,
                            reinterpret_cast<const double2*>(spec), phase, weight, partial, nsub,
@@ -1424,8 +1423,8 @@ int ppf_gaussian_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin, int32_t nga
   double* taus = nullptr;
   if (scat) {
     const size_t nb = (size_t)nrow * nbin;
-    if (int r = ensure(ctx, ctx->aux, (nb + (size_t)nrow) * sizeof(double))) return r;
-    rows = static_cast<double*>(ctx->aux.p);
+    if (int r = ensure(ctx, ctx->buf[kAux], (nb + (size_t)nrow) * sizeof(double))) return r;
+    rows = static_cast<double*>(ctx->buf[kAux].p);
     taus = rows + nb;
   }
   if (int r = timed(ctx, PPF_K_MODEL_FFT, [&] {
@@ -1438,11 +1437,7 @@ int ppf_gaussian_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin, int32_t nga
   return timed(ctx, PPF_K_MODEL_FFT, [&] {
     hipLaunchKernelGGL(k_scat_taus, dim3((nrow + 255) / 256), dim3(256), 0, ctx->stream, freqs,
                        nrow, params[1] / (double)nbin, alpha, nu_ref, taus);
-    if (logN < 0)
-      hipLaunchKernelGGL(k_rotate_rows_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin),
-                         ctx->stream, rows, nullptr, taus, out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rotate_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, rows, nullptr, taus, out, tw));
+    launch_rotate_rows(ctx->stream, logN, nbin, nrow, rows, nullptr, taus, out, tw);
   });
 }
 

@@ -208,3 +208,42 @@ def test_pipeline_pieces_bitwise(eng, pieces):
         for k in ["params", "param_errs", "nu_out", "cov", "scales", "red_chi2", "snr", "nfev",
                   "status"]:
             np.testing.assert_array_equal(o[k], ref[k], err_msg=k)
+
+
+def test_pipeline_mixed_tau_bitwise(eng):
+    """Subints that start with tau != 0 (tau not fitted) leave the Taylor path
+    for the pipeline's k_solve<true> leg.  Mixed with Taylor subints, over
+    ragged pieces and several chunks, every result is bitwise that of one
+    queue."""
+    nsub, nchan, nbin = 26, 32, 256
+    w = synth.make_workload(nsub, nchan, nbin, seed=321)
+    data = synth.workload_data_host(w)
+    nu = O.guess_fit_freq(w.freqs)
+    init = np.zeros((nsub, 5))
+    init[:, 1] = w.DM0
+    init[::3, 3] = 1e-3
+    args = (data, w.model, w.freqs, w.P, init, [1, 1, 0, 0, 0])
+
+    def run():
+        eng.reset_kernel_times()
+        out = _np(eng.fit_batch(*args, nu_fit=[nu, nu, nu], guess=True))
+        return out, eng.kernel_time("data_xspec")[1]
+
+    try:
+        eng.set_timing(True)
+        eng.set_pipeline(1)
+        ref, _ = run()
+        eng.set_pipeline(3)
+        out, n_whole = run()
+        eng.set_workspace_limit(900000)  # ~104 KB a subint: chunks of 8, 8, 8, 2
+        out2, n_chunked = run()
+    finally:
+        eng.set_timing(False)
+        eng.set_pipeline(0)
+        eng.set_workspace_limit(32 << 30)
+    # one data pass per piece: 3 + 3 + 3 + 2 against 3
+    assert n_chunked > 3 and n_chunked > n_whole, (n_whole, n_chunked)
+    for o in (out, out2):
+        assert o.keys() == ref.keys()
+        for k in ref:
+            assert np.array_equal(o[k], ref[k]), k
