@@ -13,12 +13,12 @@ import time
 import numpy as np
 
 from . import archive as _arch
+from .engine import FitPipeline, get_engine
 from .mjd import MJD, add_days_parts, epoch_parts
-from .pplib import (DataBunch, F0_fact, phase_transform, guess_fit_freq, read_model,
-                    load_spline_model_file,
-                    read_model_device, gen_gaussian_portraits_device, scattering_alpha,
-                    weighted_mean, write_TOAs)
-from .pptoaslib import report_failure
+from .pplib import (DataBunch, F0_fact, phase_transform, gen_gaussian_portraits_device,
+                    guess_fit_freq, scattering_alpha, scattering_times, weighted_mean, write_TOAs)
+from .pptoaslib import phase_shifts, report_failure
+from .templates import TemplateSource, chan_bw, row_keys
 from .toas import TOA, TOABlock, TOAList, FlagColumn, MJDArray  # noqa: F401
 
 max_nfile = 999
@@ -164,7 +164,6 @@ def fit_pipeline(keys):
     """The batched-fit pipeline get_TOAs submits its pieces to
     (engine.FitPipeline on this process's device).  The CPU tests replace it
     at this boundary with pptoaslib.SyncPipeline over a stand-in fit."""
-    from .engine import FitPipeline, get_engine
     return FitPipeline(get_engine(), keys=keys)
 
 
@@ -215,129 +214,89 @@ class GetTOAs:
             raise SystemExit("Too many archives.  See/change max_nfile(=%d)." % max_nfile)
         self.is_FITS_model = _arch.file_is_type(modelfile, "FITS")
         self.modelfile = modelfile
+        self._templates = None
         for a in _LIST_ATTRS:
             setattr(self, a, [])
         self.TOA_list = TOAList()
         self.instrumental_response_dict = self.ird = {"DM": 0.0, "wids": [], "irf_types": []}
         self.quiet = quiet
 
-    def _fits_model(self, nchan_data=None):
-        """The FITS-archive template of get_TOAs (pptoas.py:323-338): tscrunched,
-        baseline removed, masked; [nchan, nbin] (a 1-channel template tiled)."""
-        md = _arch.load_data(self.modelfile, dedisperse=False, dededisperse=False,
-                             tscrunch=True, pscrunch=True, rm_baseline=True, quiet=True)
-        model = np.asarray((md.masks * md.subints)[0, 0])
-        if md.nchan == 1 and nchan_data is not None:
-            model = np.tile(model[0], nchan_data).reshape(nchan_data, md.nbin)
-        return md, model
-
-    @staticmethod
-    def _row_keys(rows):
-        """First-appearance index of every distinct row, and each row's index
-        into those (np.unique on the rows, renumbered in order of appearance)."""
-        rows = np.ascontiguousarray(rows)
-        if (rows == rows[0]).all():
-            return np.zeros(1, dtype=np.int64), np.zeros(len(rows), dtype=np.int64)
-        v = rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).ravel()
-        _, first, inv = np.unique(v, return_index=True, return_inverse=True)
-        order = np.argsort(first, kind="stable")
-        rank = np.empty_like(order)
-        rank[order] = np.arange(len(order))
-        return first[order], rank[inv.ravel()]
-
-    # -- per-subint templates ------------------------------------------------
-    def _models(self, data, fit_scat, quiet, uniform_freqs=False):
-        """Template portrait per ok subint (pptoas.py:351-378), de-duplicated:
-        one device build per distinct (channel frequencies, P when TAU is in
-        bins of P) key."""
-        nsub = data.nsub
-        if self.is_FITS_model:
-            md, model = self._fits_model(data.nchan)
-            if md.nbin != data.nbin or md.nchan != data.nchan:  # pptoas.py:329-338
-                return None
-            return np.asarray(model)[None], np.zeros(nsub, dtype=np.int32), None
-        try:
-            info = read_model(self.modelfile, quiet=True)
-        except UnboundLocalError:  # not a .gmodel: a ppspline model (pptoas.py:375-378)
-            return self._spline_models(data)
-        name, code, nu_ref, ngauss, gparams, mflags, alpha, fit_alpha = info
-        self.model_name, self.ngauss = name, ngauss
-        if fit_scat:
-            self.model_code, self.model_nu_ref = code, nu_ref
-            self.gparams, self.alpha = gparams, alpha
-        tau_P = gparams[1] != 0 and not fit_scat
-        ok = np.asarray(data.ok_isubs)
-        if uniform_freqs and not tau_P:
-            first, inv = np.zeros(1, dtype=np.int64), np.zeros(len(ok), dtype=np.int64)
-        else:
-            keyrows = data.freqs[ok]
-            if tau_P:
-                keyrows = np.concatenate([keyrows, data.Ps[ok][:, None]], axis=1)
-            first, inv = self._row_keys(keyrows)
-        idx = np.zeros(nsub, dtype=np.int32)
-        idx[ok] = inv
-        keyf = data.freqs[ok[first]]
-        keyP = data.Ps[ok[first]]
-        nbin = len(data.phases)
-        models = np.empty((len(first), data.nchan, nbin))
-        params = np.array(gparams, dtype=float)
-        if fit_scat:
-            params[1] = 0.0
-            models[:] = gen_gaussian_portraits_device(code, params, 0.0, nbin, keyf, nu_ref)
-        elif not tau_P:
-            models[:] = gen_gaussian_portraits_device(code, params, alpha, nbin, keyf, nu_ref)
-        else:  # read_model's TAU * nbin / P differs per period
-            for P in sorted(set(keyP.tolist())):
-                sel = np.flatnonzero(keyP == P)
-                pp = np.copy(params)
-                pp[1] *= nbin / P
-                models[sel] = gen_gaussian_portraits_device(code, pp, alpha, nbin, keyf[sel],
-                                                            nu_ref)
-        return models, idx, None
-
-    def _spline_models(self, data):
-        """ppspline templates: read_spline_model(modelfile, freqs[isub], nbin)
-        per subint (pptoas.py:375-378), one device build per distinct channel
-        frequency row (ppf_spline_portraits)."""
-        name, source, datafile, mean_prof, eigvec, tck = load_spline_model_file(self.modelfile)
-        self.model_name = name
-        ok = np.asarray(data.ok_isubs)
-        first, inv = self._row_keys(data.freqs[ok])
-        idx = np.zeros(data.nsub, dtype=np.int32)
-        idx[ok] = inv
-        from .engine import get_engine
-        models = get_engine().spline_portraits(mean_prof, eigvec, tck, data.freqs[ok[first]],
-                                               len(data.phases)).cpu().numpy()
-        return models, idx, None
+    @property
+    def templates(self):
+        """The TemplateSource of modelfile (templates.py), parsed on first use.
+        It builds Gaussian portraits with this module's gen_gaussian_portraits_
+        device: like fit_pipeline, the boundary where the CPU tests put the
+        host restatement in place of the device."""
+        if self._templates is None:
+            self._templates = TemplateSource(self.modelfile, self.is_FITS_model,
+                                             gen_gaussian_portraits_device)
+        return self._templates
 
     def _irf_active(self):
         return bool(getattr(self, "add_instrumental_response", False)) and \
             bool(self.ird["DM"] or len(self.ird["wids"]))
 
-    def _irf_models(self, models, midx, data, isubs):
-        """Templates convolved with the instrumental response of each subint
-        (pptoas.py:387-393: instrumental_response_port_FT(nbin, freqsx, DM, P,
-        wids, irf_types) times rfft(modelx)), on the device.  The response
-        depends on the subint only through P (DM smearing) and chan_bw =
-        |freqsx[1] - freqsx[0]| of its ok channels; rows are convolved at
-        every channel (masked ones are not fitted).  A one-channel subint,
-        where the reference's chan_bw raises IndexError, gets chan_bw 0."""
-        from .engine import get_engine
-        eng = get_engine()
-        ird = self.ird
-        out, keys, idx = [], {}, np.zeros(data.nsub, dtype=np.int32)
-        for isub in isubs:
-            fx = data.freqs[isub, data.ok_ichans[isub]]
-            cbw = abs(fx[1] - fx[0]) if len(fx) > 1 else 0.0
-            P = data.Ps[isub]
-            key = (int(midx[isub]), data.freqs[isub].tobytes(), cbw, P if ird["DM"] else None)
-            if key not in keys:
-                keys[key] = len(out)
-                out.append(eng.instrumental_response_rows(
-                    models[midx[isub]], data.freqs[isub], ird["DM"], P, ird["wids"],
-                    ird["irf_types"], chan_bw=cbw).cpu().numpy())
-            idx[isub] = keys[key]
-        return np.stack(out), idx
+    # -- per-subint templates (policy here, mechanism in templates.py) -------
+    def _models(self, data, fit_scat, uniform_freqs=False):
+        """get_TOAs' templates (pptoas.py:323-393) and each subint's index into
+        them, or None on an archive template's nbin/nchan mismatch: the model
+        with the subint's own P, unscattered under fit_scat, one per distinct
+        frequency row (and P when TAU is in bins of P); then the response
+        with that P and the chan_bw of the ok channels, at every channel
+        (masked ones are not fitted), one per distinct (template, frequency
+        row, chan_bw, P when ird["DM"])."""
+        src = self.templates
+        ok = np.asarray(data.ok_isubs)
+        idx = np.zeros(data.nsub, dtype=np.int32)
+        if src.kind == "fits":
+            md, model = src.fits(data.nchan)
+            if md.nbin != data.nbin or md.nchan != data.nchan:  # pptoas.py:329-338
+                return None
+            models = np.asarray(model)[None]
+        else:
+            self.model_name = src.name
+            tau_P = False
+            if src.kind == "gmodel":
+                self.ngauss = src.ngauss
+                if fit_scat:
+                    self.model_code, self.model_nu_ref = src.code, src.nu_ref
+                    self.gparams, self.alpha = np.copy(src.gparams), src.alpha
+                tau_P = src.gparams[1] != 0 and not fit_scat
+            if uniform_freqs and not tau_P:
+                first, inv = np.zeros(1, dtype=np.int64), np.zeros(len(ok), dtype=np.int64)
+            else:
+                keyrows = data.freqs[ok]
+                if tau_P:
+                    keyrows = np.concatenate([keyrows, data.Ps[ok][:, None]], axis=1)
+                first, inv = row_keys(keyrows)
+            idx[ok] = inv
+            models = src.portraits(data.freqs[ok[first]], len(data.phases), data.Ps[ok[first]],
+                                   scattered=not fit_scat)
+        if self._irf_active():
+            ird, P = self.ird, data.Ps[ok]
+            cbw = np.array([chan_bw(data.freqs[i, data.ok_ichans[i]]) for i in ok])
+            first, inv = row_keys(np.column_stack([idx[ok], data.freqs[ok], cbw,
+                                                   P if ird["DM"] else 0 * P]))
+            models = np.stack([src.respond(models[idx[ok[j]]], data.freqs[ok[j]], P[j], cbw[j],
+                                           ird) for j in first])
+            idx[ok] = inv
+        return models, idx
+
+    @staticmethod
+    def _channel_rows(data, isubs, skip_channels=None):
+        """Every ok channel of subints isubs, in (isub, ok channel) order: the
+        data rows [n, nbin], their load_data noise (nan where the archive has
+        none) and the subint and channel index of each; skip_channels
+        ([nchan] bool) drops those channels."""
+        chans = [np.asarray(data.ok_ichans[i], dtype=np.int64) for i in isubs]
+        isub = np.repeat(np.asarray(isubs, dtype=np.int64), [len(c) for c in chans])
+        ichan = np.concatenate(chans) if chans else np.zeros(0, dtype=np.int64)
+        if skip_channels is not None:
+            keep = ~skip_channels[ichan]
+            isub, ichan = isub[keep], ichan[keep]
+        ns = data.get("noise_stds")
+        noise = np.full(len(isub), np.nan) if ns is None else np.asarray(ns)[isub, 0, ichan]
+        return np.asarray(data.subints)[isub, 0, ichan], noise, isub, ichan
 
     def _open(self, datafile, tscrunch, quiet, rm_base=None):
         """open_archive as get_TOAs loads (pptoas.py:250-264): no
@@ -537,8 +496,6 @@ class GetTOAs:
         self.add_instrumental_response = add_instrumental_response
         start = time.time()
         datafiles = self.datafiles if datafile is None else [datafile]
-        from .pplib import get_bin_centers
-        from .engine import get_engine
         for iarch, datafile in enumerate(datafiles):
             try:
                 data = self._load(datafile, tscrunch, quiet, rm_baseline)
@@ -556,67 +513,45 @@ class GetTOAs:
             obs = DataBunch(telescope=data.telescope, backend=data.backend,
                             frontend=data.frontend)
             MJDs = np.array([data.epochs[i].in_days() for i in range(nsub)], dtype=np.double)
-            mweights = None
-            if self.is_FITS_model:
-                md, model = self._fits_model()
+            # the model at freqs[isub] with TAU in bins of Ps[isub] (pptoas.py:888-915):
+            # one template per distinct (frequency row, P)
+            src = self.templates
+            ok = np.asarray(data.ok_isubs)
+            midx = np.zeros(nsub, dtype=np.int64)
+            skip = None
+            if src.kind == "fits":
+                md, model = src.fits(nchan)
                 if md.nbin != nbin:
                     if not quiet:
                         print("Model nbin %d != data nbin %d for %s; skipping it." % (
                             md.nbin, nbin, name))
                     continue
-                if md.nchan == 1:
-                    model = np.tile(model[0], nchan).reshape(nchan, nbin)
-                elif md.nchan != nchan:
+                if md.nchan not in (1, nchan):
                     if not quiet:
                         print("Model nchan %d != data nchan %d for %s; skipping it." % (
                             md.nchan, nchan, name))
                     continue
-                mweights = np.asarray(md.weights)[0]
-            models, midx = [], {}
-            rows, mrows, noise, where = [], [], [], []
-            subints = np.asarray(data.subints)
-            irf = self._irf_active()
-            spline = None
-            for isub in data.ok_isubs:
-                f = data.freqs[isub]
-                kk = ("fits",) if self.is_FITS_model else (f.tobytes(), data.Ps[isub])
-                if irf:  # modelx convolved per subint (pptoas.py:920-926)
-                    kk = kk + (int(isub),)
-                key = midx.setdefault(kk, len(models))
-                if key == len(models):
-                    if self.is_FITS_model:
-                        m = model
-                    else:
-                        try:
-                            m = read_model_device(self.modelfile, nbin, f, data.Ps[isub],
-                                                  quiet=True)[2]
-                        except UnboundLocalError:  # ppspline model (pptoas.py:912-915)
-                            if spline is None:
-                                spline = load_spline_model_file(self.modelfile)
-                            m = get_engine().spline_portraits(spline[3], spline[4], spline[5],
-                                                              f, nbin).cpu().numpy()
-                    if irf:
-                        fx = f[data.ok_ichans[isub]]
-                        cbw = abs(fx[1] - fx[0]) if len(fx) > 1 else 0.0
-                        m = get_engine().instrumental_response_rows(
-                            np.asarray(m, dtype=np.float64), f, self.ird["DM"], data.Ps[isub],
-                            self.ird["wids"], self.ird["irf_types"], chan_bw=cbw).cpu().numpy()
-                    models.append(m)
-                for ichan in data.ok_ichans[isub]:
-                    if mweights is not None and mweights[ichan] == 0:
-                        continue
-                    rows.append(subints[isub, 0, ichan])
-                    mrows.append(key * nchan + ichan)
-                    ns = data.get("noise_stds")
-                    noise.append(np.nan if ns is None else ns[isub, 0, ichan])
-                    where.append((int(isub), int(ichan)))
+                skip = np.asarray(md.weights)[0] == 0  # pptoas.py:966
+                models = np.asarray(model)[None]
+            else:
+                first, midx[ok] = row_keys(np.column_stack([data.freqs[ok], data.Ps[ok]]))
+                models = src.portraits(data.freqs[ok[first]], nbin, data.Ps[ok[first]])
+            if self._irf_active():
+                # modelx convolved per subint, with its P and the chan_bw of
+                # its ok channels (pptoas.py:920-926)
+                models = np.stack([src.respond(
+                    models[midx[i]], data.freqs[i], data.Ps[i],
+                    chan_bw(data.freqs[i, data.ok_ichans[i]]), self.ird) for i in ok])
+                midx[ok] = np.arange(len(ok))
+            rows, noise, isub, ichan = self._channel_rows(data, ok, skip)
+            mrows = (midx[isub] * nchan + ichan).astype(np.int32)
+            where = list(zip(isub.tolist(), ichan.tolist()))
             t0 = time.time()
             out = np.zeros((0, 6))
-            if rows:
-                mstack = np.concatenate(models, axis=0)
+            if len(rows):
                 out = get_engine().phase_shift_batch(
-                    np.array(rows), mstack, noise=np.array(noise), Ns=100,
-                    bounds=(-0.5, 0.5), model_idx=np.array(mrows, dtype=np.int32)).cpu().numpy()
+                    rows, models.reshape(-1, nbin), noise=noise, Ns=100, bounds=(-0.5, 0.5),
+                    model_idx=mrows).cpu().numpy()
             fit_duration = time.time() - t0
             z = lambda *sh: np.zeros(sh, dtype=np.float64)
             phis, phi_errs = z(nsub, nchan), z(nsub, nchan)
@@ -688,21 +623,38 @@ class GetTOAs:
         subint, the data row, its rotate_portrait_full phase, its template
         row (de-duplicated templates + row index), the fitted scale, the
         scattering time [rot] and the channel noise."""
-        from .pptoaslib import phase_shifts
-        from .pplib import scattering_times
         ok_files = list(np.array(self.datafiles)[self.ok_idatafiles])
         ifile = ok_files.index(datafile)
         # rm_baseline=True as in show_fit; archives reach this build already
         # loaded (PSRCHIVE's baseline removal is out of scope, archive.py)
         data = self._load(datafile, getattr(self, "tscrunch", False), quiet, True)
-        nbin = data.nbin
-        irf = self._irf_active()
-        spline = None
-        subints = np.asarray(data.subints)
-        models, mkeys = [], {}
-        rows, ph, mrow, sc, taus, noise, where = [], [], [], [], [], [], []
+        nsub, nchan, nbin = data.nsub, data.nchan, data.nbin
+        isubs = np.asarray(isubs, dtype=np.int64)
+        # show_fit's template (pptoas.py:1356-1388): unscattered where the
+        # fitted tau != 0 (the fit's tau scatters it), else the model with TAU
+        # in bins of data.Ps.mean(); one per distinct (frequency row, tau != 0)
+        src = self.templates
+        midx = np.zeros(nsub, dtype=np.int64)
+        models = np.zeros((0, nchan, nbin))
+        if src.kind == "fits":
+            models = np.asarray(src.fits(nchan)[1], dtype=np.float64)[None]
+        elif len(isubs):
+            scat = np.asarray(self.taus[ifile])[isubs] != 0.0
+            first, midx[isubs] = row_keys(np.column_stack([data.freqs[isubs], scat]))
+            f, scat = data.freqs[isubs[first]], scat[first]
+            models = np.empty((len(first), nchan, nbin))
+            if scat.any():
+                models[scat] = src.portraits(f[scat], nbin, scattered=False)
+            if not scat.all():
+                models[~scat] = src.portraits(f[~scat], nbin, data.Ps.mean())
+        if self._irf_active() and len(isubs):
+            # the subint's P and the full freqs row (pptoas.py:1382-1388), so
+            # chan_bw is |freqs[1] - freqs[0]| over all channels
+            models = np.stack([src.respond(models[midx[i]], data.freqs[i], data.Ps[i],
+                                           chan_bw(data.freqs[i]), self.ird) for i in isubs])
+            midx[isubs] = np.arange(len(isubs))
+        phase, tau_ch = np.zeros((nsub, nchan)), np.zeros((nsub, nchan))
         for isub in isubs:
-            phi = self.phis[ifile][isub]
             DM = self.DMs[ifile][isub]
             GM = self.GMs[ifile][isub]
             if self.bary:  # pptoas.py:1348-1350, whatever was fitted
@@ -710,65 +662,19 @@ class GetTOAs:
                 GM /= self.doppler_fs[ifile][isub] ** 3
             freqs = data.freqs[isub]
             nu_ref_DM, nu_ref_GM, nu_ref_tau = self.nu_refs[ifile][isub]
-            P = data.Ps[isub]
+            phase[isub] = phase_shifts(self.phis[ifile][isub], DM, GM, freqs, nu_ref_DM,
+                                       nu_ref_GM, data.Ps[isub])
             tau = self.taus[ifile][isub]
-            if self.is_FITS_model:
-                key = ("fits",)
-            elif tau != 0.0:
-                key = ("unscattered", freqs.tobytes())
-            else:
-                key = ("model", freqs.tobytes())
-            if irf:  # the response depends on the subint (pptoas.py:1382-1388)
-                key = key + (int(isub),)
-            if key not in mkeys:
-                mkeys[key] = len(models)
-                if self.is_FITS_model:
-                    md, m = self._fits_model(len(freqs))
-                elif tau != 0.0:
-                    info = read_model(self.modelfile, quiet=True)
-                    gparams = np.copy(info[4])
-                    gparams[1] = 0.0
-                    m = gen_gaussian_portraits_device(info[1], gparams, 0.0, nbin, freqs, info[2])
-                else:
-                    try:
-                        m = read_model_device(self.modelfile, nbin, freqs, data.Ps.mean(),
-                                              quiet=True)[2]
-                    except UnboundLocalError:  # ppspline model (pptoas.py:1380-1381)
-                        if spline is None:
-                            spline = load_spline_model_file(self.modelfile)
-                        from .engine import get_engine
-                        m = get_engine().spline_portraits(spline[3], spline[4], spline[5],
-                                                          freqs, nbin).cpu().numpy()
-                if irf:
-                    # show_fit passes the full freqs row (pptoas.py:1384-1386),
-                    # so chan_bw is |freqs[1] - freqs[0]| over all channels
-                    cbw = abs(freqs[1] - freqs[0]) if len(freqs) > 1 else 0.0
-                    from .engine import get_engine
-                    m = get_engine().instrumental_response_rows(
-                        np.asarray(m, dtype=np.float64), freqs, self.ird["DM"], P,
-                        self.ird["wids"], self.ird["irf_types"], chan_bw=cbw).cpu().numpy()
-                models.append(np.asarray(m, dtype=np.float64))
-            k = mkeys[key]
-            phs = phase_shifts(phi, DM, GM, freqs, nu_ref_DM, nu_ref_GM, P)
             if tau != 0.0:
-                t = 10 ** tau if self.log10_tau else tau
-                tch = scattering_times(t, self.alphas[ifile][isub], freqs, nu_ref_tau)
-            else:
-                tch = np.zeros(len(freqs))
-            ns = data.get("noise_stds")
-            for ichan in data.ok_ichans[isub]:
-                rows.append(subints[isub, 0, ichan])
-                ph.append(phs[ichan])
-                mrow.append(k * data.nchan + ichan)
-                sc.append(self.scales[ifile][isub][ichan])
-                taus.append(tch[ichan])
-                noise.append(np.nan if ns is None else ns[isub, 0, ichan])
-                where.append((int(isub), int(ichan)))
-        return DataBunch(data=data, ifile=ifile, rows=np.array(rows).reshape(-1, nbin),
-                         phase=np.array(ph), models=np.concatenate(models, 0) if models else
-                         np.zeros((0, nbin)), model_row=np.array(mrow, dtype=np.int32),
-                         scale=np.array(sc), tau=np.array(taus), noise=np.array(noise),
-                         where=where)
+                tau_ch[isub] = scattering_times(10 ** tau if self.log10_tau else tau,
+                                                self.alphas[ifile][isub], freqs, nu_ref_tau)
+        rows, noise, isub, ichan = self._channel_rows(data, isubs)
+        return DataBunch(data=data, ifile=ifile, rows=rows, phase=phase[isub, ichan],
+                         models=models.reshape(-1, nbin),
+                         model_row=(midx[isub] * nchan + ichan).astype(np.int32),
+                         scale=np.asarray(self.scales[ifile])[isub, ichan],
+                         tau=tau_ch[isub, ichan], noise=noise,
+                         where=list(zip(isub.tolist(), ichan.tolist())))
 
     def show_fit(self, datafile=None, isub=0, rotate=0.0, show=True, return_fit=False,
                  savefig=False, quiet=None):
@@ -781,7 +687,6 @@ class GetTOAs:
             quiet = self.quiet
         if datafile is None:
             datafile = self.datafiles[0]
-        from .engine import get_engine
         eng = get_engine()
         fr = self._fitted_rows(datafile, [isub], quiet)
         data = fr.data
@@ -812,7 +717,6 @@ class GetTOAs:
         goes to the device in one ppf_resid_chi2_rows call (rotation,
         scattering, scaling and the chi2 sum fused per channel); the
         thresholds and the iterated S/N cut run on the host as there."""
-        from .engine import get_engine
         eng = get_engine()
         for iarch, ok_idatafile in enumerate(self.ok_idatafiles):
             datafile = self.datafiles[ok_idatafile]
@@ -890,14 +794,12 @@ class GetTOAs:
         # GIL); equal weight rows make the mask rows equal too
         ru = _par_map(rows_equal, [data.freqs, data.weights])
         uniform = {"freqs": ru[0], "weights": ru[1], "mask": ru[1] or rows_equal(mask)}
-        mm = self._models(data, fit_scat, quiet, uniform["freqs"])
+        mm = self._models(data, fit_scat, uniform["freqs"])
         if mm is None:
             if not quiet:
                 print("Model nbin/nchan mismatch for %s; skipping it." % datafile)
             return None
-        models, midx, _ = mm
-        if self._irf_active():
-            models, midx = self._irf_models(models, midx, data, ok_isubs)
+        models, midx = mm
         nchx = np.count_nonzero(wn, axis=1)
         allok = nchx == nchan
         # the tobs flag's values: typed when the durations are numbers
@@ -1039,7 +941,6 @@ class GetTOAs:
         s_lo, s_hi = int(subs[0]), int(subs[-1]) + 1
         full = job.arch.read(s_lo, s_hi)  # [s_hi - s_lo, npol, nchan, nbin], numpy or device
         if data.get("snr_deferred"):
-            from .engine import get_engine
             data.SNRs[s_lo:s_hi] = get_engine().profile_snr(full).cpu().numpy()
             self._nu_fit_and_tau(data, subs, job.wn, job.allok, job.nu_fit_tuple, fit_scat,
                                  job.nu_fits_a, job.init, job.guess_tau, job.uniform["freqs"])

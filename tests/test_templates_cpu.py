@@ -2,7 +2,8 @@
 gen_spline_portrait (pplib.py:932-956) and instrumental_response_port_FT
 (pptoaslib.py:145-179) against the reference's own outputs
 (tests/golden/make_golden_r3.py), and the host side of the spline-model
-reader (restricted unpickler, read_model's "not a .gmodel" signal)."""
+reader (restricted unpickler, read_model's "not a .gmodel" signal), and the
+de-duplication of template keys (templates.row_keys)."""
 import io
 import json
 import os
@@ -100,3 +101,21 @@ def test_oracle_instrumental_response(fx):
         R = O.instrumental_response_port_FT(m["nbin"], z["irf_%s_freqs" % tag], m["DM"],
                                             m["P"], m["wids"], m["irf_types"])
         np.testing.assert_allclose(np.real(R), np.real(z["irf_" + tag]), rtol=0, atol=1e-15)
+
+
+def test_row_keys():
+    """templates.row_keys: first-appearance index of every distinct row and
+    each row's index into those."""
+    from pulseportraiture_amd.templates import row_keys
+    a, b, c = [1.0, 2.0, 3.0], [1.0, 2.0, 3.5], [0.5, 2.0, 3.0]
+    first, inv = row_keys(np.array([a, a, a]))  # identical rows: one key
+    assert first.tolist() == [0] and inv.tolist() == [0, 0, 0]
+    # distinct rows out of (sorted) order: numbered as they first appear
+    rows = np.array([b, c, b, a, c, a])
+    first, inv = row_keys(rows)
+    assert first.tolist() == [0, 1, 3] and inv.tolist() == [0, 1, 0, 2, 1, 2]
+    assert np.array_equal(rows[first][inv], rows)
+    first, inv = row_keys(np.array([c]))  # a single row
+    assert first.tolist() == [0] and inv.tolist() == [0]
+    first, inv = row_keys(np.array([a, a, b])[:, ::2])  # a non-contiguous view
+    assert first.tolist() == [0, 2] and inv.tolist() == [0, 0, 1]
