@@ -30,6 +30,11 @@
  *   ppf_scatter_rotate_rows <- GetTOAs.show_fit port/model  pptoas.py:1389-1402
  *   ppf_resid_chi2_rows     <- pplib.get_red_chi2 per channel in
  *                              GetTOAs.get_channels_to_zap  pptoas.py:1201-1278
+ *   ppf_pca_portraits       <- pplib.pca                       pplib.py:1497-1534
+ *                              (as ppspline.make_spline_model calls it,
+ *                              ppspline.py:67-82, batched over portraits)
+ *   ppf_pca_project         <- pplib.reconstruct_portrait and the projection
+ *                              pplib.py:1536-1553, ppspline.py:119-129
  *   ppf_synth_portraits     <- (test/bench input producer; pplib.make_fake_pulsar
  *                              math, pplib.py:3342-3377, on device)
  *
@@ -101,7 +106,8 @@ extern "C" {
 #define PPF_K_MOMENTS 12
 #define PPF_K_RESID 13
 #define PPF_K_UNPACK 14
-#define PPF_NUM_KERNELS 15
+#define PPF_K_PCA 15
+#define PPF_NUM_KERNELS 16
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -298,6 +304,44 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin,
                           const double* data, const double* model,
                           const int32_t* model_idx, const double* noise,
                           int32_t Ns, double lo, double hi, double* out);
+
+/* Principal components of nport portraits (pplib.pca, pplib.py:1497-1534):
+ * mean_prof[p] = sum_n w[p][n] port[p][n] / sum_n w[p][n] (channels in
+ * order), and the ncomp leading eigenvalues (descending) and unit
+ * eigenvectors of np.cov((port[p] - mean_prof[p]).T, aweights=w[p], ddof=1).
+ * They are the squared singular values and right singular vectors of
+ * A[n] = sqrt(w_n / fact) (port[n] - mean), fact = sum w - sum w^2 / sum w,
+ * from a one-sided Jacobi on A's rows in fp64 (ppfit_pca.hip): no nbin x
+ * nbin matrix is formed, and of the reference's nbin eigenvectors at most
+ * min(nchan, nbin) exist here (the rest span the null space).  Rows whose
+ * |row|^2 is at most eps^2 nbin times the largest are null and left as they
+ * are: the vectors of eigenvalues that small (rank-deficient input: at most
+ * nchan - 1 are non-zero) are unit vectors of no meaning, or zeros.
+ *   Sign: each vector's largest-magnitude component, the first on ties, is
+ * positive (LAPACK's is arbitrary).  Results are bitwise reproducible and do
+ * not depend on how many portraits share the call.
+ *   2 <= nchan <= 2048 rows, 1 <= ncomp <= min(nchan, nbin).  Weights are
+ * finite and >= 0 with at least two > 0 per portrait (PPF_ERR_INVALID
+ * otherwise: fact would be 0); a zero-weight row contributes nothing.
+ *   info[p] = {sweeps made, 1 if converged (a sweep without a rotation)
+ * within 30 sweeps else 0}.  The copy of A is workspace
+ * (ppf_set_workspace_limit splits the call over portraits).  The call
+ * synchronises the stream once per sweep.                                  */
+int ppf_pca_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                      const double* port /* [nport][nchan][nbin] */,
+                      const double* weights /* [nport][nchan] */, int32_t ncomp,
+                      double* mean_prof /* [nport][nbin] */, double* eigval /* [nport][ncomp] */,
+                      double* eigvec /* [nport][ncomp][nbin]: vectors as rows */,
+                      int32_t* info /* [nport][2] */);
+
+/* proj[p][n][e] = (port[p][n] - mean_prof[p]) . eigvec[p][e] and, when
+ * reconst is not NULL, reconst[p][n] = sum_e proj[p][n][e] eigvec[p][e] +
+ * mean_prof[p] (reconstruct_portrait, pplib.py:1536-1553).  nchan <= 2048,
+ * 1 <= ncomp <= min(2048, nbin); proj [nport][nchan][ncomp], reconst
+ * [nport][nchan][nbin].                                                    */
+int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
+                    const double* mean_prof, int32_t ncomp, const double* eigvec, double* proj,
+                    double* reconst);
 
 /* out[r] = irfft(rfft(in[r]) * exp(2 pi i k phase[r]))  (rotate_data)     */
 int ppf_rotate_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,

@@ -1529,4 +1529,131 @@ int ppf_resid_chi2_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* 
   });
 }
 
+int ppf_pca_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
+                      const double* weights, int32_t ncomp, double* mean_prof, double* eigval,
+                      double* eigvec, int32_t* info) {
+  if (!ctx || !port || !weights || !mean_prof || !eigval || !eigvec || !info)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nport <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  if (nchan < 2) return fail(ctx, PPF_ERR_INVALID, "nchan=%d: a PCA needs at least 2 rows", nchan);
+  if (nchan > kPcaMaxRows)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: at most %d rows per portrait", nchan,
+                kPcaMaxRows);
+  if (ncomp < 1 || ncomp > std::min(nchan, nbin))
+    return fail(ctx, PPF_ERR_INVALID, "ncomp=%d: 1..min(nchan, nbin)=%d", ncomp,
+                std::min(nchan, nbin));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the weights are checked on the host: fact = sum w - sum w^2 / sum w must be > 0
+  std::vector<double> hw((size_t)nport * nchan);
+  HIPCHK(ctx, hipMemcpyAsync(hw.data(), weights, hw.size() * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int p = 0; p < nport; ++p) {
+    int npos = 0;
+    for (int n = 0; n < nchan; ++n) {
+      const double w = hw[(size_t)p * nchan + n];
+      if (!std::isfinite(w) || w < 0.0)
+        return fail(ctx, PPF_ERR_INVALID, "portrait %d: weight %d is %g (need finite, >= 0)", p, n,
+                    w);
+      npos += w > 0.0;
+    }
+    if (npos < 2)
+      return fail(ctx, PPF_ERR_INVALID, "portrait %d: %d positive weights (need at least 2)", p,
+                  npos);
+  }
+  // per portrait: A [nchan][nbin], |row|^2 [nchan], the state, the order [ncomp]
+  const int m = nchan, M = (m + 1) & ~1;
+  const size_t bA = (size_t)m * nbin * sizeof(double), bN = (size_t)m * sizeof(double);
+  const size_t bO = (size_t)ncomp * sizeof(int);
+  const size_t per_port = bA + bN + sizeof(PcaState) + bO;
+  // portraits per pass: under the workspace limit and the grid's y extent
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)nport, ctx->ws_limit / (int64_t)(per_port + 1024), 65535}));
+  const size_t oN = align256((size_t)chunk * bA), oS = align256(oN + (size_t)chunk * bN);
+  const size_t oO = align256(oS + (size_t)chunk * sizeof(PcaState));
+  if (int r = ensure(ctx, ctx->buf[kWs], oO + (size_t)chunk * bO)) return r;
+  char* base = static_cast<char*>(ctx->buf[kWs].p);
+  double* A = reinterpret_cast<double*>(base);
+  double* norm2 = reinterpret_cast<double*>(base + oN);
+  PcaState* state = reinterpret_cast<PcaState*>(base + oS);
+  int* order = reinterpret_cast<int*>(base + oO);
+  std::vector<PcaState> hs((size_t)chunk);
+  for (int64_t p0 = 0; p0 < nport; p0 += chunk) {
+    const int np = (int)std::min<int64_t>(chunk, nport - p0);
+    HIPCHK(ctx, hipMemsetAsync(state, 0, (size_t)np * sizeof(PcaState), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(order, 0, (size_t)np * bO, ctx->stream));
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_pca_center, dim3((nbin + kBlock - 1) / kBlock, np), dim3(kBlock), 0,
+                             ctx->stream, port + (size_t)p0 * m * nbin, weights + (size_t)p0 * m,
+                             m, nbin, mean_prof + (size_t)p0 * nbin, A);
+        }))
+      return r;
+    // the host reads the portraits' states once per sweep and stops when
+    // every one is done (converged, or kPcaMaxSweeps sweeps made)
+    for (int sweep = 0; sweep <= kPcaMaxSweeps; ++sweep) {
+      if (int r = timed(ctx, PPF_K_PCA, [&] {
+            hipLaunchKernelGGL(k_pca_norms, dim3(m, np), dim3(kBlock), 0, ctx->stream, A, m, nbin,
+                               norm2);
+            hipLaunchKernelGGL(k_pca_sweep, dim3(np), dim3(kBlock), 0, ctx->stream, state, norm2,
+                               m, nbin, sweep, kPcaMaxSweeps);
+          }))
+        return r;
+      HIPCHK(ctx, hipMemcpyAsync(hs.data(), state, (size_t)np * sizeof(PcaState),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      bool all_done = true;
+      for (int p = 0; p < np; ++p) all_done = all_done && hs[p].done != 0;
+      if (all_done) break;
+      if (int r = timed(ctx, PPF_K_PCA, [&] {
+            for (int round = 0; round < M - 1; ++round)
+              hipLaunchKernelGGL(k_pca_step, dim3(M / 2, np), dim3(kBlock), 0, ctx->stream, A,
+                                 state, m, M, nbin, round);
+          }))
+        return r;
+    }
+    // (norm2 holds the final rows' norms: a done portrait is not rotated again)
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_pca_rank, dim3(np), dim3(kBlock), bN, ctx->stream, norm2, m, ncomp,
+                             order);
+          hipLaunchKernelGGL(k_pca_emit, dim3(ncomp, np), dim3(kBlock), 0, ctx->stream, A, norm2,
+                             order, state, m, nbin, ncomp, eigval + (size_t)p0 * ncomp,
+                             eigvec + (size_t)p0 * ncomp * nbin, info + (size_t)p0 * 2);
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
+int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
+                    const double* mean_prof, int32_t ncomp, const double* eigvec, double* proj,
+                    double* reconst) {
+  if (!ctx || !port || !mean_prof || !eigvec || !proj)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nport <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  if (nchan < 1) return fail(ctx, PPF_ERR_INVALID, "nchan=%d", nchan);
+  if (nchan > kPcaMaxRows)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: at most %d rows per portrait", nchan,
+                kPcaMaxRows);
+  if (ncomp < 1 || ncomp > std::min<int>(kPcaMaxRows, nbin))
+    return fail(ctx, PPF_ERR_INVALID, "ncomp=%d: 1..%d", ncomp, std::min<int>(kPcaMaxRows, nbin));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  for (int64_t p0 = 0; p0 < nport; p0 += 65535) {  // the grid's y extent
+    const int np = (int)std::min<int64_t>(65535, nport - p0);
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_pca_project, dim3(nchan, np), dim3(kBlock),
+                             (size_t)ncomp * sizeof(double), ctx->stream,
+                             port + (size_t)p0 * nchan * nbin, mean_prof + (size_t)p0 * nbin,
+                             eigvec + (size_t)p0 * ncomp * nbin, nchan, nbin, ncomp,
+                             proj + (size_t)p0 * nchan * ncomp,
+                             reconst ? reconst + (size_t)p0 * nchan * nbin : nullptr);
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
 }  // extern "C"

@@ -710,6 +710,16 @@ struct SplineArgs {
   const double* eigvec;         // [nbin][neig]
 };
 
+// one portrait of the Jacobi PCA (ppfit_pca.hip)
+constexpr int kPcaMaxRows = 2048, kPcaMaxSweeps = 30;
+struct PcaState {
+  int rot;        // rotations made in the running sweep
+  int done;       // no further sweeps: converged, or out of sweeps
+  int sweeps;     // sweeps started
+  int converged;  // the last sweep rotated nothing
+  double null2;   // |row|^2 at or below which a row is null in this sweep
+};
+
 constexpr int kMaxIrf = 16;
 struct IrArgs {
   int nw;                 // instrumental responses besides the DM smearing

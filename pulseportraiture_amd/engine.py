@@ -613,6 +613,56 @@ class Engine:
         out._keep = (f, mean, evd)
         return out.reshape(shape + (nb,))
 
+    def pca_portraits(self, port, weights, ncomp=None):
+        """pplib.pca (pplib.py:1497-1534) of portraits [..., nchan, nbin] with
+        weights [..., nchan] in one call (ppf_pca_portraits): the weighted
+        mean profile [..., nbin], the ncomp (default min(nchan, nbin)) leading
+        eigenvalues [..., ncomp] and eigenvectors as rows [..., ncomp, nbin]
+        of the weighted covariance, and info [..., 2] (sweeps, converged).
+        Device tensors in, device tensors out."""
+        dev = self.device
+        x = _dev_f64(port, dev)
+        lead = tuple(x.shape[:-2])
+        nchan, nbin = int(x.shape[-2]), int(x.shape[-1])
+        x = x.reshape(-1, nchan, nbin)
+        nport = int(x.shape[0])
+        w = _dev_f64(weights, dev, (nport, nchan))
+        nc = min(nchan, nbin) if ncomp is None else int(ncomp)
+        shp = max(nc, 0)
+        mean = torch.empty((nport, nbin), dtype=torch.float64, device=dev)
+        eigval = torch.empty((nport, shp), dtype=torch.float64, device=dev)
+        eigvec = torch.empty((nport, shp, nbin), dtype=torch.float64, device=dev)
+        info = torch.zeros((nport, 2), dtype=torch.int32, device=dev)
+        self._chk(self.lib.ppf_pca_portraits(self.ctx, nport, nchan, nbin, _ptr(x), _ptr(w), nc,
+                                             _ptr(mean), _ptr(eigval), _ptr(eigvec), _ptr(info)))
+        mean._keep = (x, w)
+        return (mean.reshape(lead + (nbin,)), eigval.reshape(lead + (shp,)),
+                eigvec.reshape(lead + (shp, nbin)), info.reshape(lead + (2,)))
+
+    def pca_project(self, port, mean_prof, eigvec, reconstruct=False):
+        """Projections [..., nchan, ncomp] of (port - mean_prof) on the
+        eigenvectors (rows, [..., ncomp, nbin]) and, with reconstruct, the
+        portrait rebuilt from them (reconstruct_portrait, pplib.py:1536-1553;
+        ppf_pca_project).  Returns (proj, reconst or None), device tensors."""
+        dev = self.device
+        x = _dev_f64(port, dev)
+        lead = tuple(x.shape[:-2])
+        nchan, nbin = int(x.shape[-2]), int(x.shape[-1])
+        x = x.reshape(-1, nchan, nbin)
+        nport = int(x.shape[0])
+        mean = _dev_f64(mean_prof, dev, (nport, nbin))
+        v = _dev_f64(eigvec, dev)
+        nc = int(v.shape[-2])
+        v = v.reshape(nport, nc, nbin)
+        proj = torch.empty((nport, nchan, nc), dtype=torch.float64, device=dev)
+        rec = torch.empty((nport, nchan, nbin), dtype=torch.float64, device=dev) \
+            if reconstruct else None
+        self._chk(self.lib.ppf_pca_project(self.ctx, nport, nchan, nbin, _ptr(x), _ptr(mean), nc,
+                                           _ptr(v), _ptr(proj), _ptr(rec)))
+        proj._keep = (x, mean, v)
+        return (proj.reshape(lead + (nchan, nc)),
+                rec.reshape(lead + (nchan, nbin)) if reconstruct else None)
+
     def _irf_call(self, nrow, nbin, rows, f, fh, DM, P, wids, irf_types, chan_bw, out):
         code = {"rect": 0, "gauss": 1}
         types = []
@@ -849,7 +899,8 @@ def _on_engine_stream(fn):
 
 
 for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portraits",
-              "spline_portraits", "instrumental_response_rows", "response_table", "tscrunch",
+              "spline_portraits", "pca_portraits", "pca_project", "instrumental_response_rows",
+              "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "spec_cache", "rotate_accumulate_spec",
               "synth"):

@@ -791,20 +791,5 @@ def _single_channel(u, archives, model_port, npol, accum, tw, dev):
 
 def _normalize(port, method, get_noise):
     """normalize_portrait for the final template (pplib.py:2462-2507)."""
-    out = np.zeros(port.shape)
-    for i in range(len(port)):
-        if not port[i].any():
-            continue
-        if method == "mean":
-            nrm = port[i].mean()
-        elif method == "max":
-            nrm = port[i].max()
-        elif method == "rms":
-            nrm = get_noise(port[i])
-        elif method == "abs":
-            nrm = (port[i] ** 2).sum() ** 0.5
-        else:
-            good = np.where(port.sum(axis=1) != 0.0)[0]
-            nrm = fit_phase_shift(port[i], np.average(port[good], axis=0)).scale
-        out[i] = port[i] / nrm
-    return out
+    from .pplib import normalize_portrait
+    return normalize_portrait(port, method, get_noise=get_noise)

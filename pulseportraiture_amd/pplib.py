@@ -453,6 +453,140 @@ def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100):
                      snr=out[4], red_chi2=out[5], duration=time.time() - t0)
 
 
+def normalize_portrait(port, method="rms", weights=None, return_norms=False,
+                       get_noise=None):
+    """Normalize each profile of a portrait, pplib.py:2462-2507: by its mean,
+    its maximum, its fitted scale against the (weighted) mean profile
+    ('prof', fit_phase_shift on the device), its noise level ('rms',
+    get_noise) or its length ('abs').  All-zero rows stay zero with norm 1."""
+    if method not in ("mean", "max", "prof", "rms", "abs"):
+        print("Unknown method for normalize_portrait(...), '%s'." % method)
+        return None
+    noise = get_noise if get_noise is not None else globals()["get_noise"]
+    port = np.asarray(port)
+    norm_port = np.zeros(port.shape)
+    norm_vals = np.ones(len(port))
+    if method == "prof":
+        good = np.where(port.sum(axis=1) != 0.0)[0]
+        w = None if weights is None else np.asarray(weights)[good]
+        mean_prof = np.average(port[good], axis=0, weights=w)
+    for i in range(len(port)):
+        if not port[i].any():
+            continue
+        if method == "mean":
+            nrm = port[i].mean()
+        elif method == "max":
+            nrm = port[i].max()
+        elif method == "prof":
+            nrm = fit_phase_shift(port[i], mean_prof).scale
+        elif method == "rms":
+            nrm = noise(port[i])
+        else:
+            nrm = (port[i] ** 2).sum() ** 0.5
+        norm_port[i] = port[i] / nrm
+        norm_vals[i] = nrm
+    if return_norms:
+        return norm_port, norm_vals
+    return norm_port
+
+
+# ---------------------------------------------------------------------------
+# PCA of a portrait and the choice of eigenvectors (ppspline model building)
+# ---------------------------------------------------------------------------
+def pca(port, mean_prof=None, weights=None, quiet=False, ncomp=None):
+    """Principal components of an nchan x nbin portrait, pplib.py:1497-1534,
+    on the device (ppf_pca_portraits: a one-sided Jacobi on the centred,
+    weighted rows; no nbin x nbin covariance is formed).
+
+    Returns eigval [r] (descending) and eigvec [nbin, r] (column vectors),
+    r = ncomp or min(nchan, nbin): the reference's remaining nbin - r columns
+    span the null space of the covariance (their eigenvalues are rounding
+    noise) and are not returned; of the r, at most nchan - 1 eigenvalues are
+    non-zero.  Each vector's largest-magnitude component is positive
+    (LAPACK's sign is arbitrary).  As in the reference, mean_prof does not
+    change the covariance (np.cov centres by the weighted mean itself), so
+    it is not used.  weights: nchan values >= 0, default equal."""
+    port = np.asarray(port, dtype=np.float64)
+    nmes, ndim = port.shape
+    if not quiet:
+        print("Performing principal component analysis on data with %d dimensions and %d "
+              "measurements..." % (ndim, nmes))
+    if weights is None:
+        weights = np.ones(nmes)
+    _, eigval, eigvec, _ = _engine().pca_portraits(port, np.asarray(weights, dtype=np.float64),
+                                                   ncomp)
+    return eigval.cpu().numpy(), np.ascontiguousarray(eigvec.cpu().numpy().T)
+
+
+def reconstruct_portrait(port, mean_prof, eigvec):
+    """The portrait projected into the space of the column vectors eigvec
+    [nbin, ncomp], pplib.py:1536-1553 (ppf_pca_project)."""
+    eigvec = np.asarray(eigvec, dtype=np.float64)
+    port = np.asarray(port, dtype=np.float64)
+    if eigvec.shape[1] == 0:
+        return np.tile(np.asarray(mean_prof, dtype=np.float64), (len(port), 1))
+    return _engine().pca_project(port, mean_prof, np.ascontiguousarray(eigvec.T),
+                                 reconstruct=True)[1].cpu().numpy()
+
+
+def count_crossings(x, x0):
+    """Number of crossings of the 1-D array x across the threshold x0,
+    pplib.py:686-694 (an exact hit counts once, not twice)."""
+    d = np.asarray(x) - x0
+    return (np.diff(np.sign(d)) != 0).sum() - (d == 0).sum()
+
+
+_NO_SMOOTH = ("wavelet smoothing is unpinned: PyWavelets is not available to pin it against "
+              "(only try_nlevels=0, the identity, is implemented)")
+
+
+def find_significant_eigvec(eigvec, check_max=10, return_max=10, snr_cutoff=150.0,
+                            check_crossings=True, check_acorr=True, return_smooth=False,
+                            noise=None, **kwargs):
+    """Indices of the "significant" eigenvectors (columns of eigvec
+    [nbin, ncomp]), pplib.py:1555-1619, with the reference's control flow --
+    its borderline `elif`, which can never add a vector, included.  The
+    smoothing is the identity (the reference's try_nlevels=0 path of
+    smart_smooth); return_smooth=True or another try_nlevels raises
+    NotImplementedError.  Other smart_smooth keywords (rchi2_tol, ...) are
+    accepted and unused.  noise: the vectors' get_noise values if already
+    known (default: get_noise of the examined vectors, on the device)."""
+    if return_smooth or kwargs.get("try_nlevels", 0) not in (0, None):
+        raise NotImplementedError(_NO_SMOOTH)
+    eigvec = np.asarray(eigvec, dtype=np.float64)
+    ncheck = min(max(check_max, return_max), eigvec.shape[1])
+    if noise is None and ncheck:
+        noise = get_noise(np.ascontiguousarray(eigvec.T[:ncheck]), chans=True)
+    ieig = []
+    for ivec in range(ncheck):  # (the reference always has nbin columns)
+        add_eigvec = False
+        ev = eigvec.T[ivec]
+        ev_noise = noise[ivec] * np.sqrt(len(ev) / 2.0)
+        ev_snr = np.sum(np.abs(np.fft.rfft(ev)[1:]) ** 2) / ev_noise
+        if ev_snr >= snr_cutoff:
+            if check_crossings and ev_snr < 3 * snr_cutoff:
+                ncross = count_crossings(abs(ev), 0.1 * abs(ev).max())
+                if ncross < int(0.02 * len(ev)):
+                    add_eigvec = True
+            elif check_acorr and ev_snr < 3 * snr_cutoff and add_eigvec:
+                acorr = np.correlate(ev, ev, "same")
+                fwhm = acorr.argmax() - np.where(acorr > acorr.max() / 2.0)[0].min()
+                if fwhm > 5:
+                    add_eigvec = True
+                else:
+                    add_eigvec = False
+                    print("Borderline case eigenvector %d failed test." % ivec)
+            else:
+                add_eigvec = True
+        if add_eigvec:
+            ieig.append(ivec)
+        if ivec + 1 == check_max:
+            break
+        if len(ieig) == return_max:
+            break
+    return np.array(ieig, dtype=int)
+
+
 def fit_portrait(data, model, init_params, P, freqs, nu_fit=None, nu_out=None, errs=None,
                  bounds=[(None, None), (None, None)], id=None, quiet=True):
     """Legacy phase + DM fit (pplib.py:2102-2204) on the GPU.

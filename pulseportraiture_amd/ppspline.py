@@ -1,0 +1,254 @@
+"""ppspline drop-in: B-spline portrait models from a PCA of an averaged portrait.
+
+For an nchan x nbin portrait of aligned profiles (ppalign's output) the model
+is a B-spline representation of the curve the nchan profiles trace in the
+space of a few eigenprofiles (ppspline.py:1-20).  The PCA runs on the device
+(ppf_pca_portraits, batched over portraits), as do the projections
+(ppf_pca_project) and the model portraits (ppf_spline_portraits); the curve
+fit is one scipy.interpolate.splprep call per model on nchan x <= 10 numbers
+(FITPACK, third-party to the reference too).
+
+Not here: wavelet smoothing (smooth=True; PyWavelets is not available to pin
+it against), metafile / joinfile portraits, plotting and the command line.
+Without smoothing the reference's S/N test lets noise eigenvectors through at
+large nbin, so callers should set max_ncomp.
+"""
+import pickle
+
+import numpy as np
+
+from . import archive as _arch
+from . import pplib
+from .pplib import get_noise, gen_spline_portrait, find_significant_eigvec
+
+_NO_SMOOTH = ("smooth=True: " + pplib._NO_SMOOTH)
+
+
+def spline_smoothing(nprof, SNRs, noise_stds, sfac=1.0):
+    """The smoothing condition s handed to splprep (ppspline.py:136-138)."""
+    SNRs = np.asarray(SNRs, dtype=np.float64)
+    return sfac * nprof * np.sum((SNRs * np.asarray(noise_stds)) ** 2) / sum(SNRs) ** 2
+
+
+def fit_spline_curve(proj_port, weights, freqs, s, bw=1.0, k=3, max_nbreak=None, quiet=True,
+                     splprep=None):
+    """The B-spline curve traced by the projected profiles, parameterized by
+    frequency (ppspline.py:139-155): splprep over the rows in increasing
+    frequency (reversed when bw < 0), refitted with at most max_nbreak
+    breakpoints (nest = max_nbreak + 2 k; s = inf at two) if the first fit
+    has more.  Returns (tck, u), fp, ier, msg.  splprep: the fitting
+    function (default scipy.interpolate.splprep)."""
+    if splprep is None:
+        from scipy.interpolate import splprep
+    flip = -1 if bw < 0 else 1  # u in splprep has to be increasing
+    x = list(np.asarray(proj_port)[::flip].T)
+    w, u = np.asarray(weights)[::flip], np.asarray(freqs)[::flip]
+    nu_lo, nu_hi = np.min(freqs), np.max(freqs)
+    (tck, u_out), fp, ier, msg = splprep(x, w=w, u=u, ub=nu_lo, ue=nu_hi, k=k, task=0, s=s,
+                                         t=None, full_output=1, nest=None, per=0,
+                                         quiet=int(quiet))
+    if max_nbreak is not None and len(np.unique(tck[0])) > max_nbreak:
+        if max_nbreak < 2:
+            print("max_nbreak not >= 2; setting max_nbreak = 2...")
+            max_nbreak = 2
+        if max_nbreak == 2:
+            s = np.inf
+        (tck, u_out), fp, ier, msg = splprep(x, w=w, u=u, ub=nu_lo, ue=nu_hi, k=k, task=0, s=s,
+                                             t=None, full_output=1, nest=max_nbreak + (k * 2),
+                                             per=0, quiet=int(quiet))
+    return (tck, u_out), fp, ier, msg
+
+
+class DataPortrait(object):
+    """The data to which a model is fitted (pplib.py:139-327, one archive): a
+    PSRFITS file, an .npz, or a registered / dict archive, loaded dedispersed,
+    tscrunched and pscrunched.  port is the masked portrait, portx its
+    unzapped channels; likewise freqs / freqsxs, noise_stds / noise_stdsxs
+    and SNRs / SNRsxs."""
+
+    def __init__(self, datafile, quiet=False, joinfile=None):
+        if joinfile is not None:
+            raise NotImplementedError("joinfile portraits are not supported")
+        if _arch.file_is_type(datafile, "ASCII"):
+            raise NotImplementedError("metafile portraits are not supported: %s lists archives; "
+                                      "give one averaged archive" % datafile)
+        self.njoin = 0
+        self.join_params, self.join_ichans, self.all_join_params = [], [], []
+        self.data = _arch.load_data(datafile, dedisperse=True, dededisperse=False, tscrunch=True,
+                                    pscrunch=True, fscrunch=False, flux_prof=True,
+                                    refresh_arch=True, return_arch=True, quiet=quiet)
+        self.datafile = datafile if isinstance(datafile, str) else self.data.filename
+        self.datafiles = [self.datafile]
+        for key in self.data.keys():
+            setattr(self, key, self.data[key])
+        if self.source is None:
+            self.source = "noname"
+        self.subints = _arch.host_array(self.subints)
+        self.weights = np.asarray(self.weights, dtype=np.float64)
+        self.masks = np.asarray(self.masks)
+        self.port = (self.masks * self.subints)[0, 0]
+        if self.noise_stds is None:
+            self.noise_stds = get_noise(self.subints[0, 0], chans=True)[None, None]
+        self.noise_stds = np.array(self.noise_stds, dtype=np.float64)
+        self.SNRs = np.array(self.SNRs, dtype=np.float64)
+        ok = self.ok_ichans[0]
+        self.portx = self.port[ok]
+        self.flux_prof = self.port.mean(axis=1)
+        self.flux_profx = self.flux_prof[ok]
+        self.freqsxs = [self.freqs[0, ok]]
+        self.noise_stdsxs = self.noise_stds[0, 0, ok]
+        self.SNRsxs = self.SNRs[0, 0, ok]
+        self.norm_values = np.ones(len(self.port))
+
+    def normalize_portrait(self, method="rms"):
+        """Normalize each channel's profile (pplib.py:357-382)."""
+        if method not in ("mean", "max", "prof", "rms", "abs"):
+            print("Unknown method for normalize_portrait(...), '%s'." % method)
+            return
+        if method == "prof":
+            weights = self.weights[0]
+            weightsx = self.weights[self.weights > 0]
+        else:
+            weights = weightsx = None
+        self.unnorm_noise_stds = np.copy(self.noise_stds)
+        self.port, self.norm_values = pplib.normalize_portrait(self.port, method, weights=weights,
+                                                               return_norms=True)
+        self.noise_stds[0, 0] = get_noise(self.port, chans=True)
+        self.flux_prof = self.port.mean(axis=1)
+        self.unnorm_noise_stdsxs = np.copy(self.noise_stdsxs)
+        self.portx = pplib.normalize_portrait(self.portx, method, weights=weightsx,
+                                              return_norms=False)
+        self.noise_stdsxs = get_noise(self.portx, chans=True)
+        self.flux_profx = self.portx.mean(axis=1)
+
+    def unnormalize_portrait(self):
+        """Undo normalize_portrait (pplib.py:384-398)."""
+        if hasattr(self, "unnorm_noise_stds"):
+            self.port = (self.norm_values * self.port.transpose()).transpose()
+            self.noise_stds = np.copy(self.unnorm_noise_stds)
+            del self.unnorm_noise_stds
+            self.flux_prof = self.port.mean(axis=1)
+            self.portx = (self.norm_values[self.ok_ichans[0]] * self.portx.transpose()).transpose()
+            self.noise_stdsxs = np.copy(self.unnorm_noise_stdsxs)
+            del self.unnorm_noise_stdsxs
+            self.flux_profx = self.portx.mean(axis=1)
+            self.norm_values = np.ones(len(self.port))
+
+    def pca_weights(self):
+        """The PCA (and spline) weights of the unzapped channels (ppspline.py:69)."""
+        return self.SNRsxs / np.sum(self.SNRsxs)
+
+    def make_spline_model(self, max_ncomp=10, smooth=False, snr_cutoff=150.0, rchi2_tol=0.1, k=3,
+                          sfac=1.0, max_nbreak=None, model_name=None, quiet=False, **kwargs):
+        """Make a model based on PCA and B-spline interpolation
+        (ppspline.py:34-204; the arguments are the reference's).
+
+        smooth defaults to False, unlike the reference: smooth=True (wavelet
+        smoothing of the eigenvectors and mean profile) raises
+        NotImplementedError.  **kwargs go to find_significant_eigvec."""
+        make_spline_models([self], max_ncomp=max_ncomp, smooth=smooth, snr_cutoff=snr_cutoff,
+                           rchi2_tol=rchi2_tol, k=k, sfac=sfac, max_nbreak=max_nbreak,
+                           model_names=[model_name], quiet=quiet, **kwargs)
+
+    def _finish_model(self, mean_prof, eigval, eigvec, max_ncomp, snr_cutoff, rchi2_tol, k, sfac,
+                      max_nbreak, model_name, quiet, kwargs):
+        """make_spline_model after the PCA (ppspline.py:83-204); eigvec
+        [nbin, r] column vectors."""
+        port = self.portx
+        pca_weights = self.pca_weights()
+        freqs = self.freqsxs[0]
+        return_max = 10 if max_ncomp is None else min(max_ncomp, 10)
+        ieig = find_significant_eigvec(eigvec, check_max=10, return_max=return_max,
+                                       snr_cutoff=snr_cutoff, return_smooth=False,
+                                       rchi2_tol=rchi2_tol, **kwargs)
+        ncomp = len(ieig)
+        nfull = len(self.freqs[0])
+        if ncomp == 0:  # a model with the constant average portrait
+            proj_port = port[:, :0]
+            modelx = reconst_port = np.tile(mean_prof, (len(freqs), 1))
+            model = np.tile(mean_prof, (nfull, 1))
+            (tck, u) = [np.array([]), np.array([]), 0], np.array([])
+            fp, ier, msg = None, None, None
+        else:
+            basis = np.ascontiguousarray(eigvec[:, ieig])
+            proj, rec = pplib._engine().pca_project(port, mean_prof,
+                                                    np.ascontiguousarray(basis.T),
+                                                    reconstruct=True)
+            proj_port, reconst_port = proj.cpu().numpy(), rec.cpu().numpy()
+            s = spline_smoothing(len(proj_port), self.SNRsxs, self.noise_stdsxs, sfac)
+            (tck, u), fp, ier, msg = fit_spline_curve(proj_port, pca_weights, freqs, s, self.bw,
+                                                      k, max_nbreak, quiet)
+            if ier > 1:
+                print("Something went wrong in si.splprep for %s:\n%s" % (self.source, msg))
+            # both portraits in one device call
+            both = gen_spline_portrait(mean_prof, np.concatenate([freqs, self.freqs[0]]), basis,
+                                       tck)
+            modelx, model = both[:len(freqs)], both[len(freqs):]
+        self.ieig, self.ncomp = ieig, ncomp
+        self.eigvec, self.eigval, self.mean_prof = eigvec, eigval, mean_prof
+        self.proj_port, self.reconst_port = proj_port, reconst_port
+        self.tck, self.u, self.fp, self.ier, self.msg = tck, u, fp, ier, msg
+        self.model_name = self.datafile + ".spl" if model_name is None else model_name
+        self.model, self.modelx = model, modelx
+        self.model_masked = self.model * self.masks[0, 0]
+        if not quiet:
+            if proj_port.sum():
+                print("B-spline interpolation model %s uses %d basis profile components and %d "
+                      "breakpoints (%d B-splines with k=%d)." % (
+                          self.model_name, ncomp, len(np.unique(self.tck[0])),
+                          len(self.tck[0]) - self.tck[2] - 1, self.tck[2]))
+            else:
+                print("B-spline interpolation model %s uses 0 basis profile components; it "
+                      "returns the average profile." % self.model_name)
+
+    def write_model(self, outfile, quiet=False):
+        """Write the model as the reference's pickle (ppspline.py:206-230):
+        [model_name, source, datafile, mean_prof, eigvec[:, ieig], tck], in
+        protocol 2 so that the Python-2 reference reads it too."""
+        basis = self.eigvec[:, self.ieig] if len(self.ieig) else self.eigvec[:, []]
+        blob = pickle.dumps([self.model_name, self.source, self.datafile, self.mean_prof,
+                             np.ascontiguousarray(basis), self.tck], protocol=2)
+        # numpy 2 names its array constructor numpy._core.multiarray, which a
+        # Python-2 numpy does not have; numpy.core.multiarray resolves in
+        # both.  (Protocol 2 writes a global as the text "c<module>\n<name>\n",
+        # so the substitution cannot touch a length field.)
+        blob = blob.replace(b"cnumpy._core.multiarray\n", b"cnumpy.core.multiarray\n")
+        with open(outfile, "wb") as of:
+            of.write(blob)
+        if not quiet:
+            print("Wrote modelfile %s." % outfile)
+
+
+def make_spline_models(portraits, max_ncomp=10, smooth=False, snr_cutoff=150.0, rchi2_tol=0.1,
+                       k=3, sfac=1.0, max_nbreak=None, model_names=None, quiet=False, **kwargs):
+    """make_spline_model for a list of DataPortraits whose condensed
+    portraits share one shape (pulsars x receivers): one batched PCA call,
+    then the host steps per portrait.  The results are those of the
+    one-by-one calls, exactly."""
+    if smooth:
+        raise NotImplementedError(_NO_SMOOTH)
+    portraits = list(portraits)
+    if not portraits:
+        return portraits
+    shape = portraits[0].portx.shape
+    for dp in portraits:
+        if dp.portx.shape != shape:
+            raise ValueError("make_spline_models: portraits of %s and %s unzapped channels x bins; "
+                             "one shape per call" % (shape, dp.portx.shape))
+    if model_names is None:
+        model_names = [None] * len(portraits)
+    if not quiet:
+        print("Performing principal component analysis on data with %d dimensions and %d "
+              "measurements..." % (shape[1], shape[0]))
+    mean, eigval, eigvec, info = pplib._engine().pca_portraits(
+        np.stack([dp.portx for dp in portraits]),
+        np.stack([dp.pca_weights() for dp in portraits]))
+    mean, eigval, info = mean.cpu().numpy(), eigval.cpu().numpy(), info.cpu().numpy()
+    eigvec = eigvec.cpu().numpy()
+    for i, dp in enumerate(portraits):
+        if not info[i, 1]:
+            print("PCA of %s did not converge in %d sweeps." % (dp.datafile, info[i, 0]))
+        dp.pca_info = info[i]
+        dp._finish_model(mean[i], eigval[i], np.ascontiguousarray(eigvec[i].T), max_ncomp,
+                         snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_names[i], quiet, kwargs)
+    return portraits
