@@ -894,7 +894,7 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
                           d->method == PPF_METHOD_TRUST_NCG && !wide;
   const int split = std::max(1, std::min(16, nchan / 64));
   // the two-phase sweep's rows (any block's channel range at split or more)
-  L.lds_scat = PPF_SCAT_TWO_PHASE ? scat_sweep_lds(nchan, split) : L.lds_meta;
+  L.lds_scat = scat_sweep_lds(nchan, split);
   if (split_scat) {
     if (int r = ensure(ctx, ctx->buf[kSpart],
                        (size_t)chunk * ((nchan + 7) / 8) * kScatPart * sizeof(double) +

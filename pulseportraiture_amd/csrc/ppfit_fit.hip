@@ -150,14 +150,11 @@ constexpr int kPipe = 4;
 // two): config 3 solve 13.26-13.28 -> 12.68-12.74 ms, fits bitwise the same
 // (U = 2 at three: 13.05-13.07; two-phase at two workgroups: 13.28)
 #ifndef PPF_SCAT_U
-#define PPF_SCAT_U 4
-#endif
-#ifndef PPF_SCAT_TWO_PHASE
-#define PPF_SCAT_TWO_PHASE 1
+#define PPF_SCAT_U 4  // divides the 32-step re-seed period
 #endif
 #ifndef PPF_SCAT_WG_PER_CU
-#define PPF_SCAT_WG_PER_CU (PPF_SCAT_TWO_PHASE ? 3 : 1)
-#endif  // divides the 32-step re-seed period
+#define PPF_SCAT_WG_PER_CU 3
+#endif
 
 __device__ __forceinline__ void cells_phase(const double2* __restrict__ Xr, int J, int h,
                                             double phif, double* acc) {
@@ -701,21 +698,19 @@ __device__ __forceinline__ void sweep_taylor0(const FitArgs& a, const Meta& m, c
 
 // One sweep over all fitted channels at (prm, refs).  MODE 0: f, g, H for
 // the solver (out[0..20]) and raw accumulators into acc_slot; MODE 1: the
-// with-scales Hessian pieces (out[0..29]) and per-channel wsc rows.  SCAT
+// with-scales Hessian pieces (out[0..44]) and per-channel wsc rows.  SCAT
 // compiles the scattering cell loop in; without it tau must be 0 (host-side
 // dispatch guarantees it), which keeps the phase-only kernels lean.
-// Each 8-channel group's contributions are reduced across the wave at once
-// and added into the wave's own LDS row, so nothing is carried through the
-// cell loop in registers.
-// lrow (optional, kWaves * 8 rows of LDS): each channel lane (h == 0) adds its
-// terms into its own row across groups and the block sums the rows once at
-// the end, instead of NP wave reductions per channel group.
-// [j0, j1) (multiples of 8 but the end): the fitted channels this block sums.
+// Nothing is carried through the cell loop in registers.  MODE 0: each
+// 8-channel group's terms are reduced across the wave at once and added into
+// the wave's row of red, and the block sums those rows at the end.  MODE 1:
+// each channel lane (h == 0) adds its terms into its own row of lrow
+// (kWaves * 8 rows of LDS) across groups and the block sums the rows once at
+// the end, instead of 45 wave reductions per channel group.
 template <int MODE, bool SCAT>
 __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, int s, const double* prm,
                       const double* refs, double P, double* acc_slot, double* out,
-                      double (*red)[48], const TaylorSrc& ts, double (*lrow)[48] = nullptr,
-                      int j0 = 0, int j1 = 1 << 30, double* gpart = nullptr) {
+                      double (*red)[48], const TaylorSrc& ts, double (*lrow)[48] = nullptr) {
   if constexpr (MODE == 0 && !SCAT) {
     if (ts.T && ts.same) {
       sweep_taylor0(a, m, prm, acc_slot, out, red, ts);
@@ -731,17 +726,21 @@ __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, in
   const int midx = a.model_idx ? a.model_idx[s] : 0;
   const int fm = flag_mask(a);
   constexpr int NP = MODE == 0 ? 21 : 45;
+  double* myrow = nullptr;
+  // (MODE 1 never reads red; it keeps the store because k_post<false> sits on
+  // the three-waves-per-SIMD register line, 168, and comes out at 170 without)
   if (lane < NP) red[w][lane] = 0.0;
-  double* myrow = lrow ? lrow[w * 8 + g8] : nullptr;
-  if (lrow && h == 0)
-    for (int i = 0; i < NP; ++i) myrow[i] = 0.0;
+  if constexpr (MODE == 1) {
+    myrow = lrow[w * 8 + g8];
+    if (h == 0)
+      for (int i = 0; i < NP; ++i) myrow[i] = 0.0;
+  }
   __syncthreads();
-  const int jend = min(m.nok, j1);
-  const int ngroups = (jend + 7) >> 3;
-  for (int gi = (j0 >> 3) + w; gi < ngroups; gi += kWaves) {
+  const int ngroups = (m.nok + 7) >> 3;
+  for (int gi = w; gi < ngroups; gi += kWaves) {
     const int j = gi * 8 + g8;
-    const bool valid = j < jend;
-    const int jj = valid ? j : jend - 1;
+    const bool valid = j < m.nok;
+    const int jj = valid ? j : m.nok - 1;
     const int n = m.chan[jj];
     const double fr = m.fr[jj];
     double acc[NACC];
@@ -763,56 +762,35 @@ __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, in
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = group8_sum(acc[i]);
     if constexpr (MODE == 0) {
-      if (!lrow) {
-        // f, g and H terms spread over each channel's 8 lanes: lane h forms
-        // out-slots h, h + 8, h + 16 (the channel's sums are on all 8 after
-        // group8_sum), then one chan8_sum per slot row sums the group's 8
-        // channels -- the additions wave_sum made on one lane's 21 terms, on
-        // the same operands, so every slot is bitwise as before
-        const double dpre[2] = {m.d1[jj], m.d2[jj]};
-        const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[jj], m.iw2[jj], fr, prm, tau_lin, refs,
-                                         P, log10_tau, dpre);
-        const double q = d.C * d.C / d.S;
-        const LanePick L{d.dph[0], d.dph[1], d.dph[2], d.dts[0],
-                         d.dts[1], d.d2ts[0], d.d2ts[1], d.d2ts[2]};
-        if (h == 0 && valid) {
-          double* dst = acc_slot + (size_t)j * NACC;
-          for (int i = 0; i < NACC; ++i) dst[i] = acc[i];
-        }
-        const bool on = valid;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const double v = chan8_sum(on ? mode0_term(d, L, q, h + 8 * r, fm) : 0.0);
-          const int t = (lane & 7) + 8 * r;
-          if (lane >= 8 && lane < 16 && t < NP) {
-            if (gpart) gpart[(size_t)gi * kScatPart + t] = v;  // summed by the caller
-            else red[w][t] += v;
-          }
-        }
-        continue;
-      }
-    }
-    double ct[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) ct[i] = 0.0;
-    if (h == 0 && valid) {
-      const double dpre[2] = {m.d1[j], m.d2[j]};
-      const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[j], m.iw2[j], fr, prm, tau_lin, refs, P,
-                                       log10_tau, MODE == 0 ? dpre : nullptr);
+      // f, g and H terms spread over each channel's 8 lanes: lane h forms
+      // out-slots h, h + 8, h + 16 (the channel's sums are on all 8 after
+      // group8_sum), then one chan8_sum per slot row sums the group's 8
+      // channels -- the additions wave_sum would make on one lane's 21 terms,
+      // on the same operands
+      const double dpre[2] = {m.d1[jj], m.d2[jj]};
+      const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[jj], m.iw2[jj], fr, prm, tau_lin, refs,
+                                       P, log10_tau, dpre);
       const double q = d.C * d.C / d.S;
-      if (MODE == 0) {
+      const LanePick L{d.dph[0], d.dph[1], d.dph[2], d.dts[0],
+                       d.dts[1], d.d2ts[0], d.d2ts[1], d.d2ts[2]};
+      if (h == 0 && valid) {
         double* dst = acc_slot + (size_t)j * NACC;
         for (int i = 0; i < NACC; ++i) dst[i] = acc[i];
-        ct[0] = -q;
+      }
 #pragma unroll
-        for (int i = 0; i < 5; ++i)
-          if (a.flags[i]) ct[1 + i] = -q * (2.0 * dC_(d, i) / d.C - dS_(d, i) / d.S);
+      for (int r = 0; r < 3; ++r) {
+        const double v = chan8_sum(valid ? mode0_term(d, L, q, h + 8 * r, fm) : 0.0);
+        const int t = (lane & 7) + 8 * r;
+        if (lane >= 8 && lane < 16 && t < NP) red[w][t] += v;
+      }
+    } else {
+      double ct[NP];
 #pragma unroll
-                for (int p = 0; p < 15; ++p) {
-          const int pi = pair_i(p), pj = pair_j(p);
-          if (a.flags[pi] && a.flags[pj]) ct[6 + p] = Hn_(d, pi, pj);
-        }
-      } else {
+      for (int i = 0; i < NP; ++i) ct[i] = 0.0;
+      if (h == 0 && valid) {
+        const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[j], m.iw2[j], fr, prm, tau_lin, refs, P,
+                                         log10_tau);
+        const double q = d.C * d.C / d.S;
         const double sc = d.C / d.S;
         double cross[5];
 #pragma unroll
@@ -824,7 +802,7 @@ __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, in
         for (int i = 0; i < 5; ++i) dst[2 + i] = cross[i];
         const double ic = 1.0 / (2.0 * d.S);
 #pragma unroll
-                for (int p = 0; p < 15; ++p) {
+        for (int p = 0; p < 15; ++p) {
           const int pi = pair_i(p), pj = pair_j(p);
           if (a.flags[pi] && a.flags[pj]) {
             ct[p] = -2.0 * q * ((d2C_(d, pi, pj) / d.C) - (0.5 * d2S_(d, pi, pj) / d.S));
@@ -833,29 +811,18 @@ __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, in
           }
         }
       }
-    }
-    if (lrow) {
       if (h == 0 && valid)
 #pragma unroll
         for (int i = 0; i < NP; ++i) myrow[i] += ct[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const double v = wave_sum(ct[i]);  // only h == 0 lanes hold terms
-        if (lane == 0) {
-          if (gpart) gpart[(size_t)gi * kScatPart + i] = v;  // summed by the caller
-          else red[w][i] += v;
-        }
-      }
     }
   }
   __syncthreads();
   if (tid < NP) {
     double t = 0.0;
-    if (lrow)
-      for (int r = 0; r < kWaves * 8; ++r) t += lrow[r][tid];
-    else
+    if constexpr (MODE == 0)
       for (int q = 0; q < kWaves; ++q) t += red[q][tid];
+    else
+      for (int r = 0; r < kWaves * 8; ++r) t += lrow[r][tid];
     out[tid] = t;
   }
   __syncthreads();
@@ -873,6 +840,35 @@ __device__ __forceinline__ bool fused_taylor(const FitArgs& a, int s) {
   return !((tl != 0.0) || a.flags[3]);
 }
 
+// A subint's SolveState before its fit (one thread): the starting point and
+// nu_fit from FitArgs (fmean, the mean fitted frequency, where nu_fit is NaN),
+// no evaluation yet, the family that picks its solver kernel.
+__device__ __forceinline__ void init_solve_state(const FitArgs& a, int s, double fmean,
+                                                 SolveState& st) {
+  for (int i = 0; i < 5; ++i) st.x[i] = a.init[(size_t)s * 5 + i];
+  for (int i = 0; i < 3; ++i) {
+    const double v = a.nu_fit[(size_t)s * 3 + i];
+    st.refs[i] = isnan(v) ? fmean : v;
+  }
+  st.nfev = 0;
+  st.status = -1;
+  st.slot = 0;
+  st.fun = NAN;
+  const double tl = a.log10_tau ? pow(10.0, st.x[3]) : st.x[3];
+  st.scat = (tl != 0.0) || a.flags[3];
+  st.scat_post = st.scat;
+  st.taylor = !st.scat && a.T != nullptr;
+  st.mvalid = 0;
+  st.xslot = 0;
+  st.sdone = 0;  // the split scattering solve's other fields: its first k_scat_step
+}
+
+// The starting point once the guess has set st.x[0]: init (reported as
+// init_used) and the first Taylor centre (one thread).
+__device__ __forceinline__ void fix_start_point(SolveState& st) {
+  for (int i = 0; i < 5; ++i) { st.init[i] = st.x[i]; st.xc[0][i] = st.x[i]; }
+}
+
 // Solver-state set-up and the get_TOAs initial phase of one subint (all
 // threads of the block).  dyn: >= NHP double2 of LDS for the guess spectrum.
 __device__ void guess_subint(const FitArgs& a, int c, int s, unsigned char* dyn, GuessShared& gs) {
@@ -886,33 +882,10 @@ __device__ void guess_subint(const FitArgs& a, int c, int s, unsigned char* dyn,
   cnt = block_sum(cnt, gs.red);
   const double fmean = fsum / cnt;
   SolveState& st = a.st[c];
-  if (tid == 0) {
-    for (int i = 0; i < 5; ++i) st.x[i] = a.init[(size_t)s * 5 + i];
-    for (int i = 0; i < 3; ++i) {
-      const double v = a.nu_fit[(size_t)s * 3 + i];
-      st.refs[i] = isnan(v) ? fmean : v;
-    }
-    st.nfev = 0;
-    st.status = -1;
-    st.slot = 0;
-    st.fun = NAN;
-    const double tl = a.log10_tau ? pow(10.0, st.x[3]) : st.x[3];
-    st.scat = (tl != 0.0) || a.flags[3];
-    st.scat_post = st.scat;
-    st.taylor = !st.scat && a.T != nullptr;
-    st.kit = 0;
-    st.sdone = 0;
-    st.phase = 0;
-    st.fin = 0;
-    st.mvalid = 0;
-    st.xslot = 0;
-    st.wslot = 0;
-    st.tr = 1.0;
-  }
+  if (tid == 0) init_solve_state(a, s, fmean, st);
   if (!a.guess) {
     __syncthreads();
-    if (tid == 0)
-      for (int i = 0; i < 5; ++i) { st.init[i] = st.x[i]; st.xc[0][i] = st.x[i]; }
+    if (tid == 0) fix_start_point(st);
     return;
   }
   // rm_k = R_k conj(Mm_k B_k(tau_g)): the guess template is irfft(B rfft(mean
@@ -969,7 +942,7 @@ __device__ void guess_subint(const FitArgs& a, int c, int s, unsigned char* dyn,
                  (pow(st.refs[0], -2.0) - pow(nug, -2.0)));
     if (a.guess_wrap) phi = wrap_half(phi);
     st.x[0] = phi;
-    for (int i = 0; i < 5; ++i) { st.init[i] = st.x[i]; st.xc[0][i] = st.x[i]; }
+    fix_start_point(st);
   }
 }
 
@@ -1092,29 +1065,7 @@ __global__ __launch_bounds__(64) void k_guess_w(FitArgs a) {
   const double fsum = vsum4(fv), cnt = vsum4(cv);
   const double fmean = fsum / cnt;
   SolveState& st = a.st[c];
-  if (lane == 0) {
-    for (int i = 0; i < 5; ++i) st.x[i] = a.init[(size_t)s * 5 + i];
-    for (int i = 0; i < 3; ++i) {
-      const double v = a.nu_fit[(size_t)s * 3 + i];
-      st.refs[i] = isnan(v) ? fmean : v;
-    }
-    st.nfev = 0;
-    st.status = -1;
-    st.slot = 0;
-    st.fun = NAN;
-    const double tl = a.log10_tau ? pow(10.0, st.x[3]) : st.x[3];
-    st.scat = (tl != 0.0) || a.flags[3];
-    st.scat_post = st.scat;
-    st.taylor = !st.scat && a.T != nullptr;
-    st.kit = 0;
-    st.sdone = 0;
-    st.phase = 0;
-    st.fin = 0;
-    st.mvalid = 0;
-    st.xslot = 0;
-    st.wslot = 0;
-    st.tr = 1.0;
-  }
+  if (lane == 0) init_solve_state(a, s, fmean, st);
   const double2* Rr = a.R + (size_t)c * a.NHP;
   const double tg = a.guess_tau ? a.guess_tau[s] : 0.0;
   const int NH = a.NH;
@@ -1246,7 +1197,7 @@ __global__ __launch_bounds__(64) void k_guess_w(FitArgs a) {
     phi = phi + (kDconst * DM * (1.0 / P) * (pow(st.refs[0], -2.0) - pow(nug, -2.0)));
     if (a.guess_wrap) phi = wrap_half(phi);
     st.x[0] = phi;
-    for (int i = 0; i < 5; ++i) { st.init[i] = st.x[i]; st.xc[0][i] = st.x[i]; }
+    fix_start_point(st);
   }
 }
 
@@ -1357,6 +1308,209 @@ __device__ __forceinline__ void store_grad_hess(const FitArgs& a, int s, int lan
     for (int j = 0; j < 5; ++j) a.o_hess[(size_t)s * 25 + lane * 5 + j] = ok ? Hrow[j] : NAN;
 }
 
+// A sweep's 21-double out row (0 f, 1 + i g_i, 6 + p H pair p) as this lane's
+// f, g_i and row i of H; lanes >= 5 get g = 0 and keep H
+__device__ __forceinline__ void load_fgh(const double* out, int lane, double& f, double& g,
+                                         double (&H)[5]) {
+  f = out[0];
+  g = lane < 5 ? out[1 + lane] : 0.0;
+#pragma unroll
+  for (int p = 0; p < 15; ++p) {
+    const double v = out[6 + p];
+    if (lane == pair_i(p)) H[pair_j(p)] = v;
+    if (lane == pair_j(p)) H[pair_i(p)] = v;
+  }
+}
+
+// TrustNcg parked in LDS across the sweeps every wave runs (k_fit_taylor): per
+// lane the gradient, point, last evaluated point, step and Hessian row; the
+// uniform scalars once
+struct TrustNcgLds {
+  double g[64], xl[64], xe[64], pl[64], H[5][64];
+  double f, tr, predv;
+  int hits, k, status, nfev;
+};
+
+// One trust-ncg solve, resident in one wave (the state above: lane i < 5 owns
+// component i of the vectors and row i of H, scalars are wave-uniform), as the
+// pieces of scipy's _minimize_trust_region loop that every kernel running it
+// repeats.  The kernels differ only in where the sweeps run and where this
+// state lives between them: registers (k_solve), LDS (k_fit_taylor: park /
+// unpark) or SolveState (the split scattering solve: store / load).
+//   start(); while (!done) { propose(); [sweep the proposal]; judge(); } finish();
+struct TrustNcg {
+  double f, g, xl, Hrow[5];  // accepted point: objective, gradient, point, Hessian
+  double tr, predv, pl;      // radius; the model's value at, and the step to, the proposal
+  double xe;                 // the last evaluated point (same_point8)
+  int hits, k, status, nfev;
+  double pred, rho;          // of the last judge() (solver trace), NaN where not formed
+
+  // The init evaluation at x, its f, g, H in out (not read when no channel is
+  // fitted: status -1).  True: the solve ends here.
+  __device__ __forceinline__ bool start(const double* out, const double* x, int lane, int nok,
+                                        bool eval_only) {
+    f = g = 0.0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) Hrow[j] = 0.0;
+    xl = xe = lane < 5 ? x[lane] : 0.0;
+    tr = 1.0;
+    predv = pl = 0.0;
+    hits = k = nfev = 0;
+    pred = rho = NAN;
+    status = -1;
+    if (nok == 0) return true;
+    load_fgh(out, lane, f, g, Hrow);
+    nfev = 1;
+    status = eval_only ? 1 : 0;  // PPF_SOLVE_EVAL: the objective at init only
+    return eval_only;
+  }
+
+  // The loop head: the Steihaug step pl from the accepted point and the
+  // model's value predv there; same: the proposal xl + pl repeats the last
+  // evaluated point.  False: the gradient is NaN (scipy's loop condition
+  // fails), the solve ends with status 0.
+  __device__ __forceinline__ bool propose(int lane, bool& same) {
+    const double jm = sqrt(dot8(g, g));
+    if (!(jm >= -1.0)) {
+      status = 0;
+      return false;
+    }
+    pl = steihaug(f, g, Hrow, tr, hits);
+    predv = model_val(f, g, Hrow, pl);
+    same = same_point8(lane, xl + pl, xe);
+    return true;
+  }
+
+  // The loop body after the proposal's evaluation (its f, g, H in out;
+  // counted: a fresh sweep, scipy's nfev, else the memoised repeat): the
+  // radius update and accept / reject.  accepted: the proposal is the new
+  // point.  True: the solve ends (status 2: no predicted decrease, 1: maxiter).
+  __device__ __forceinline__ bool judge(const double* out, int lane, bool counted,
+                                        bool& accepted) {
+    double fp, gp, Hp[5] = {0, 0, 0, 0, 0};
+    load_fgh(out, lane, fp, gp, Hp);
+    if (counted) {
+      nfev += 1;
+      xe = xl + pl;
+    }
+    accepted = false;
+    const double actual = f - fp;
+    pred = f - predv;
+    rho = NAN;
+    if (pred <= 0.0) {
+      status = 2;
+      return true;
+    }
+    rho = actual / pred;
+    if (rho < 0.25) tr *= 0.25;
+    else if (rho > 0.75 && hits) tr = fmin(2.0 * tr, 1000.0);
+    if (rho > 0.15) {
+      xl = xl + pl;
+      f = fp;
+      g = gp;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) Hrow[j] = Hp[j];
+      accepted = true;
+    }
+    k += 1;
+    if (k >= 1000) {
+      status = 1;
+      return true;
+    }
+    return false;
+  }
+
+  // The result (every lane of the wave calls it): x, fun, nfev, status, the
+  // accumulator half of the accepted point and k_post's variant in SolveState,
+  // scipy's jac and the Hessian in the outputs.
+  __device__ __forceinline__ void finish(const FitArgs& a, SolveState& st, int s, int lane, int nok,
+                                         int slot, bool scat) const {
+    if (lane < 5) {
+      st.x[lane] = xl;
+      store_grad_hess(a, s, lane, nok > 0, g, Hrow);
+    }
+    const double x3 = lane_at<3>(xl);
+    if (lane == 0) {
+      st.fun = nok ? f : NAN;
+      st.nfev = nok ? nfev : 0;
+      st.status = status;
+      st.slot = slot;
+      const double tl = a.log10_tau ? pow(10.0, x3) : x3;
+      st.scat_post = scat && tl != 0.0;
+    }
+  }
+
+  __device__ __forceinline__ void park(TrustNcgLds& sv, int lane) const {
+    sv.g[lane] = g;
+    sv.xl[lane] = xl;
+    sv.xe[lane] = xe;
+    sv.pl[lane] = pl;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) sv.H[j][lane] = Hrow[j];
+    if (lane == 0) {
+      sv.f = f;
+      sv.tr = tr;
+      sv.predv = predv;
+      sv.hits = hits;
+      sv.k = k;
+      sv.status = status;
+      sv.nfev = nfev;
+    }
+  }
+  // after the barrier that follows park()
+  __device__ __forceinline__ void unpark(const TrustNcgLds& sv, int lane) {
+    g = sv.g[lane];
+    xl = sv.xl[lane];
+    xe = sv.xe[lane];
+    pl = sv.pl[lane];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) Hrow[j] = sv.H[j][lane];
+    f = sv.f;
+    tr = sv.tr;
+    predv = sv.predv;
+    hits = sv.hits;
+    k = sv.k;
+    status = sv.status;
+    nfev = sv.nfev;
+  }
+
+  // A running solve between two k_scat_step launches.  xe is not kept: the
+  // next launch judges a fresh evaluation of xp = xl + pl, which sets it.
+  __device__ __forceinline__ void store(SolveState& st, int lane) const {
+    if (lane < 5) {
+      st.x[lane] = xl;
+      st.g[lane] = g;
+      for (int j = 0; j < 5; ++j) st.H[lane * 5 + j] = Hrow[j];
+      st.pl[lane] = pl;
+      st.xp[lane] = xl + pl;
+    }
+    if (lane == 0) {
+      st.fun = f;
+      st.tr = tr;
+      st.predv = predv;
+      st.hits = hits;
+      st.kit = k;
+      st.status = status;
+      st.nfev = nfev;
+    }
+  }
+  __device__ __forceinline__ void load(const SolveState& st, int lane) {
+    f = st.fun;
+    g = lane < 5 ? st.g[lane] : 0.0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) Hrow[j] = lane < 5 ? st.H[lane * 5 + j] : 0.0;
+    xl = xe = lane < 5 ? st.x[lane] : 0.0;
+    tr = st.tr;
+    predv = st.predv;
+    pl = lane < 5 ? st.pl[lane] : 0.0;
+    hits = st.hits;
+    k = st.kit;
+    status = st.status;
+    nfev = st.nfev;
+    pred = rho = NAN;
+  }
+};
+
 struct SolveShared {
   double x[5], xp[5];
   double out[48];
@@ -1382,47 +1536,22 @@ __global__ __launch_bounds__(kBlock) void k_solve(FitArgs a) {
   if (tid == 0) { sh.done = (m.nok == 0); sh.slot = 0; }
   __syncthreads();
   double* acc0 = a.acc + (size_t)c * 2 * a.nchan * NACC;
-  // wave-0 solver state (lane i < 5 owns component i; scalars are uniform)
-  double f = 0.0, g = 0.0, xl = 0.0, Hrow[5] = {0, 0, 0, 0, 0};
-  double tr = 1.0, predv = 0.0, pl = 0.0;
-  int hits = 0, k = 0, status = (m.nok == 0) ? -1 : 0, nfev = 0;
-  double xe = 0.0;  // lane i < 5: the last evaluated point (same_point8)
-  auto load_fgh = [&](double& ff, double& gg, double (&HH)[5]) {
-    ff = sh.out[0];
-    gg = lane < 5 ? sh.out[1 + lane] : 0.0;
-#pragma unroll
-    for (int p = 0; p < 15; ++p) {
-      const double v = sh.out[6 + p];
-      if (lane == pair_i(p)) HH[pair_j(p)] = v;
-      if (lane == pair_j(p)) HH[pair_i(p)] = v;
-    }
-  };
-  if (!sh.done) {
-    sweep<0, SCAT>(a, m, c, s, sh.x, refs, P, acc0, sh.out, sh.red, TaylorSrc{});
-    if (tid < 64) {
-      load_fgh(f, g, Hrow);
-      xl = lane < 5 ? sh.x[lane] : 0.0;
-      xe = xl;
-      nfev = 1;
-      if (a.solver_flags & PPF_SOLVE_EVAL) {  // objective at init only
-        status = 1;
-        if (lane == 0) sh.done = 1;
-      }
-    }
+  const bool eval_only = (a.solver_flags & PPF_SOLVE_EVAL) != 0;
+  TrustNcg tn;  // wave 0
+  if (!sh.done) sweep<0, SCAT>(a, m, c, s, sh.x, refs, P, acc0, sh.out, sh.red, TaylorSrc{});
+  if (tid < 64) {
+    const bool done = tn.start(sh.out, sh.x, lane, m.nok, eval_only);
+    if (lane == 0 && done) sh.done = 1;
   }
   __syncthreads();
   while (!sh.done) {
     if (tid < 64) {
-      const double jm = sqrt(dot8(g, g));
-      if (!(jm >= -1.0)) {  // NaN gradient: scipy's loop condition fails
-        status = 0;
-        if (lane == 0) sh.done = 1;
-      } else {
-        pl = steihaug(f, g, Hrow, tr, hits);
-        predv = model_val(f, g, Hrow, pl);
-        if (lane < 5) sh.xp[lane] = xl + pl;
-        const bool same = same_point8(lane, xl + pl, xe);
-        if (lane == 0) sh.same = same;
+      bool same = false;
+      const bool go = tn.propose(lane, same);
+      if (go && lane < 5) sh.xp[lane] = tn.xl + tn.pl;
+      if (lane == 0) {
+        sh.same = same;
+        if (!go) sh.done = 1;
       }
     }
     __syncthreads();
@@ -1434,49 +1563,16 @@ __global__ __launch_bounds__(kBlock) void k_solve(FitArgs a) {
     double* sl = acc0 + (size_t)(sh.slot ^ 1) * a.nchan * NACC;
     if (fresh) sweep<0, SCAT>(a, m, c, s, sh.xp, refs, P, sl, sh.out, sh.red, TaylorSrc{});
     if (tid < 64) {
-      double fp, gp, Hp[5] = {0, 0, 0, 0, 0};
-      load_fgh(fp, gp, Hp);
-      if (fresh) {
-        nfev += 1;
-        xe = xl + pl;
-      }
-      const double actual = f - fp;
-      const double pred = f - predv;
-      if (pred <= 0.0) {
-        status = 2;
-        if (lane == 0) sh.done = 1;
-      } else {
-        const double rho = actual / pred;
-        if (rho < 0.25) tr *= 0.25;
-        else if (rho > 0.75 && hits) tr = fmin(2.0 * tr, 1000.0);
-        if (rho > 0.15) {
-          xl = xl + pl;
-          f = fp;
-          g = gp;
-#pragma unroll
-          for (int j = 0; j < 5; ++j) Hrow[j] = Hp[j];
-          if (lane == 0) sh.slot ^= 1;
-          if (lane < 5) sh.x[lane] = xl;
-        }
-        k += 1;
-        if (k >= 1000) {
-          status = 1;
-          if (lane == 0) sh.done = 1;
-        }
+      bool accepted;
+      const bool done = tn.judge(sh.out, lane, fresh, accepted);
+      if (lane == 0) {
+        if (accepted) sh.slot ^= 1;
+        if (done) sh.done = 1;
       }
     }
     __syncthreads();
   }
-  if (tid < 5) st.x[tid] = sh.x[tid];
-  if (tid < 5) store_grad_hess(a, s, lane, m.nok > 0, g, Hrow);
-  if (tid == 0) {
-    st.fun = m.nok ? f : NAN;
-    st.nfev = m.nok ? nfev : 0;
-    st.status = status;
-    st.slot = sh.slot;
-    const double tl = a.log10_tau ? pow(10.0, sh.x[3]) : sh.x[3];
-    st.scat_post = SCAT && tl != 0.0;
-  }
+  if (tid < 64) tn.finish(a, st, s, lane, m.nok, sh.slot, SCAT);
 }
 
 // ---------------------------------------------------------------------------
@@ -1488,19 +1584,20 @@ __global__ __launch_bounds__(kBlock) void k_solve(FitArgs a) {
 //     range at the subint's point (x at init, else the proposal xp), and the
 //     per-channel accumulators into the proposal's slot;
 //   k_scat_step (one wave per subint): the per-group terms summed in the
-//     order one k_solve block sums them, then k_solve's accept / reject and
-//     the next Steihaug proposal, with the solver state kept in SolveState
-//     between launches;
+//     order one k_solve block sums them, then k_solve's TrustNcg step on them
+//     (judge, the next proposal), its state kept in SolveState between
+//     launches;
 // until no subint is left running.  Every sum is formed in k_solve<true>'s
-// order, so the trajectory, nfev, status and result are bitwise k_solve's.
+// order and the step is the same code, so the trajectory, nfev, status and
+// result are bitwise k_solve's.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ bool scat_split_owner(const FitArgs& a, const SolveState& st) {
   return a.method == PPF_METHOD_TRUST_NCG && st.scat != 0 && !st.sdone;
 }
 
 // The solver step of one subint (one wave, 64 lanes; out: kScatPart doubles
-// of LDS): the group partials summed in k_solve's order, then k_solve's
-// accept / reject and the next Steihaug proposal, the state in SolveState.
+// of LDS): the group partials summed in k_solve's order, then the TrustNcg
+// step on them, its state in SolveState.
 __device__ __forceinline__ void scat_step_wave(const FitArgs& a, const double* part, int init,
                                                int* active, double* out, int c) {
   const int s = a.sub0 + c, lane = threadIdx.x & 63;
@@ -1544,133 +1641,55 @@ __device__ __forceinline__ void scat_step_wave(const FitArgs& a, const double* p
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  auto load_fgh = [&](double& ff, double& gg, double (&HH)[5]) {
-    ff = out[0];
-    gg = lane < 5 ? out[1 + lane] : 0.0;
-#pragma unroll
-    for (int p = 0; p < 15; ++p) {
-      const double v = out[6 + p];
-      if (lane == pair_i(p)) HH[pair_j(p)] = v;
-      if (lane == pair_j(p)) HH[pair_i(p)] = v;
-    }
-  };
-  double f, g, xl, Hrow[5] = {0, 0, 0, 0, 0}, tr, predv, pl;
-  int hits, k, status, nfev, slot;
-  bool done = false;
-  // solver trace (ppf_set_trace): the point this sweep evaluated, its f, g, H
-  const double xev = lane < 5 ? (init ? st.x[lane] : st.xp[lane]) : 0.0;
-  double rho_tr = NAN, pred_tr = NAN;
-  // k_solve's post-sweep block for the point xev (whose f, g, H are in out);
-  // counted: a fresh sweep (scipy's nfev), else a repeat of the same point
-  auto advance = [&](bool counted) {
-    double fp, gp, Hp[5] = {0, 0, 0, 0, 0};
-    load_fgh(fp, gp, Hp);
-    if (counted) nfev += 1;
-    const double actual = f - fp;
-    const double pred = f - predv;
-    pred_tr = pred;
-    if (pred <= 0.0) {
-      status = 2;
-      done = true;
-    } else {
-      const double rho = actual / pred;
-      rho_tr = rho;
-      if (rho < 0.25) tr *= 0.25;
-      else if (rho > 0.75 && hits) tr = fmin(2.0 * tr, 1000.0);
-      if (rho > 0.15) {
-        xl = xl + pl;
-        f = fp;
-        g = gp;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) Hrow[j] = Hp[j];
-        slot ^= 1;
-      }
-      k += 1;
-      if (k >= 1000) { status = 1; done = true; }
-    }
-  };
+  // the evaluation in out: of x at init, else of the carried proposal
+  TrustNcg tn;
+  int slot = 0;
+  bool done, accepted = false;
   if (init) {
-    load_fgh(f, g, Hrow);
-    xl = lane < 5 ? st.x[lane] : 0.0;
-    tr = 1.0;
-    predv = pl = 0.0;
-    hits = k = status = 0;
-    nfev = 1;
-    slot = 0;
-    if (nok == 0) { status = -1; nfev = 0; done = true; }
-    if (a.solver_flags & PPF_SOLVE_EVAL) { status = 1; done = true; }
+    done = tn.start(out, st.x, lane, nok, (a.solver_flags & PPF_SOLVE_EVAL) != 0);
   } else {
-    f = st.fun;
-    g = lane < 5 ? st.g[lane] : 0.0;
-    if (lane < 5)
-      for (int j = 0; j < 5; ++j) Hrow[j] = st.H[lane * 5 + j];
-    xl = lane < 5 ? st.x[lane] : 0.0;
-    tr = st.tr;
-    predv = st.predv;
-    pl = lane < 5 ? st.pl[lane] : 0.0;
-    hits = st.hits;
-    k = st.kit;
-    status = st.status;
-    nfev = st.nfev;
+    tn.load(st, lane);
     slot = st.slot;
-    advance(true);
+    done = tn.judge(out, lane, true, accepted);
+    if (accepted) slot ^= 1;
   }
+  // solver trace (ppf_set_trace): the point this sweep evaluated, its f, g, H
   if (a.trace && nok) {
     double xv[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) xv[i] = __shfl(xev, i);
-    const int isw = nfev - 1;
+    for (int i = 0; i < 5; ++i) xv[i] = __shfl(tn.xe, i);
+    const int isw = tn.nfev - 1;
     if (lane == 0 && isw < a.trace_cap) {
       trace_sweep(a, s, isw, xv, out, 21, true);
       double* r = a.trace + ((size_t)s * a.trace_cap + isw) * kTraceRec;
-      r[28] = tr;  // radius after this evaluation's update
-      r[29] = pred_tr;
-      r[30] = rho_tr;
-      r[31] = (double)hits;  // the Steihaug boundary flag of the step that led here
+      r[28] = tn.tr;  // radius after this evaluation's update
+      r[29] = tn.pred;
+      r[30] = tn.rho;
+      r[31] = (double)tn.hits;  // the Steihaug boundary flag of the step that led here
     }
   }
-  // k_solve's loop head: NaN gradient, else the next proposal; a proposal
-  // that repeats xev (the point just evaluated) is decided on its memoised
-  // f, g, H without a sweep and without counting, as scipy's ScalarFunction
-  // does, until a new point (for the next sweep) or the end
+  // the next proposal; one that repeats the point just evaluated is decided
+  // on its memoised f, g, H (still in out) without a sweep and without
+  // counting, as scipy's ScalarFunction does, until a new point (for the next
+  // sweep) or the end
   while (!done) {
-    const double jm = sqrt(dot8(g, g));
-    if (!(jm >= -1.0)) {
-      status = 0;
+    bool same;
+    if (!tn.propose(lane, same)) {
       done = true;
       break;
     }
-    pl = steihaug(f, g, Hrow, tr, hits);
-    predv = model_val(f, g, Hrow, pl);
-    if (!same_point8(lane, xl + pl, xev)) break;
-    advance(false);
-  }
-  // state back (lanes < 5 own the vectors; lane 0 the scalars)
-  if (lane < 5) {
-    st.x[lane] = xl;
-    st.g[lane] = g;
-    for (int j = 0; j < 5; ++j) st.H[lane * 5 + j] = Hrow[j];
-    st.pl[lane] = pl;
-    st.xp[lane] = xl + pl;
-  }
-  if (done && lane < 5) store_grad_hess(a, s, lane, nok > 0, g, Hrow);
-  if (lane == 0) {
-    st.fun = nok ? f : NAN;
-    st.tr = tr;
-    st.predv = predv;
-    st.hits = hits;
-    st.kit = k;
-    st.status = status;
-    st.nfev = nok ? nfev : 0;
-    st.slot = slot;
-    if (done) st.sdone = 1;
-    else atomicAdd(active, 1);
+    if (!same) break;
+    done = tn.judge(out, lane, false, accepted);
+    if (accepted) slot ^= 1;
   }
   if (done) {
-    const double x3 = __shfl(xl, 3);
+    tn.finish(a, st, s, lane, nok, slot, true);
+    if (lane == 0) st.sdone = 1;
+  } else {
+    tn.store(st, lane);
     if (lane == 0) {
-      const double tl = a.log10_tau ? pow(10.0, x3) : x3;
-      st.scat_post = tl != 0.0;
+      st.slot = slot;
+      atomicAdd(active, 1);
     }
   }
 }
@@ -1765,11 +1784,11 @@ __device__ __forceinline__ void sweep_scat_split(const FitArgs& a, const Meta& m
 __global__ __launch_bounds__(kBlock, PPF_SCAT_WG_PER_CU) void k_scat_sweep(FitArgs a, double* part,
                                                                           int split, int init) {
   extern __shared__ __align__(16) unsigned char dyn[];
-  __shared__ SolveShared sh;
-  const int c = blockIdx.x, q = blockIdx.y, s = a.sub0 + c, tid = threadIdx.x;
+  __shared__ int s_nok;
+  const int c = blockIdx.x, q = blockIdx.y, s = a.sub0 + c;
   const SolveState& st = a.st[c];
   if (!scat_split_owner(a, st)) return;
-  const Meta m = load_meta(a, c, s, dyn, &sh.nok);
+  const Meta m = load_meta(a, c, s, dyn, &s_nok);
   if (m.nok == 0) return;
   // channel range of this block: whole groups of 8, blocks in order; each
   // group's wave-reduced terms go to part[c][group] (k_scat_step sums them
@@ -1780,18 +1799,11 @@ __global__ __launch_bounds__(kBlock, PPF_SCAT_WG_PER_CU) void k_scat_sweep(FitAr
   const double* prm = init ? st.x : st.xp;
   const int slot = init ? 0 : (st.slot ^ 1);
   double* acc = a.acc + ((size_t)c * 2 + slot) * a.nchan * NACC;
-#if PPF_SCAT_TWO_PHASE
   // the block's channel rows of group sums (dynamic LDS after the Meta arrays)
   double* chA = reinterpret_cast<double*>(dyn + scat_meta_lds(a.nchan));
   if (j0 < j1)
     sweep_scat_split(a, m, c, s, prm, st.refs, a.P[s], acc, j0, j1,
                      part + (size_t)c * ((a.nchan + 7) >> 3) * kScatPart, chA);
-#else
-  if (j0 < j1)
-    sweep<0, true>(a, m, c, s, prm, st.refs, a.P[s], acc, sh.out, sh.red, TaylorSrc{}, nullptr,
-                   j0, j1, part + (size_t)c * ((a.nchan + 7) >> 3) * kScatPart);
-#endif
-  (void)tid;
 }
 
 // The solver step of every running subint (one wave each).  ctrs: the

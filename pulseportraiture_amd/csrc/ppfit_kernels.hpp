@@ -83,23 +83,32 @@ constexpr size_t kLdsPerCU = 160 * 1024;
 constexpr int kTaylorBlocksPerCU = 3;
 constexpr double kTaylorY = 3.0;
 
-// Per-subint solver state handed from k_guess -> k_solve -> k_post (global).
+// Per-subint solver state handed from the guess kernels to the solver and on
+// to k_post (global).
 struct SolveState {
+  // every solver: set up by init_solve_state, the result read by k_post
   double x[5];     // current / final parameters
   double init[5];  // starting point (after the guess)
-  double fun;
+  double fun;      // objective at x
   double refs[3];  // nu_fit (resolved)
-  // Taylor path: expansion centres (params at refs), and the trust-ncg state
-  // saved when a proposal leaves both centres' radius (resumed after
-  // k_moments recentres)
+  int nfev, status;
+  int slot;        // accumulator half (FitArgs.acc) of the accepted point
+  int scat;        // scattering family (tau != 0 at the start, or fitted)
+  int scat_post;   // k_post's variant: tau != 0 at the final point
+  int taylor;      // phase family with the Taylor path on (FitArgs.T)
+  // Taylor path (k_moments, k_fit_taylor, k_post): the expansion centres of
+  // the two T slots (params at refs); bit q of mvalid: slot q holds moments
+  // about xc[q]; xslot: the slot that evaluated the final point
   double xc[2][5];
+  int mvalid, xslot;
+  // split scattering solve: the trust-ncg step (TrustNcg, ppfit_fit.hip)
+  // carried from one k_scat_step launch to the next -- gradient, Hessian and
+  // radius at x, the proposal xp = x + pl that k_scat_sweep evaluates, the
+  // model's value there, the Steihaug boundary flag, the iteration count --
+  // and sdone: the solve has ended
   double g[5], H[25], tr;
-  int nfev, status, slot, scat, scat_post, taylor;
-  int kit, phase, fin, mvalid, xslot, wslot;
-  // split scattering solve (k_scat_sweep / k_scat_step): the proposal, its
-  // step and predicted value, the Steihaug boundary flag, done
   double xp[5], pl[5], predv;
-  int hits, sdone;
+  int hits, kit, sdone;
 };
 
 struct FitArgs {

@@ -351,13 +351,10 @@ struct TaylorShared {
   double ifact[kMT];  // c_inv_fact for taylor_cells
   int done, nok, slot, tslot, q, mvalid;
   int same;  // the proposal repeats the last evaluated point (same_point8)
-  // wave 0's solver state between its steps (per lane: gradient, point, last
-  // evaluated point, step and Hessian row; uniform scalars once): parked here
-  // across the sweeps every wave runs, so that those registers serve the
-  // sweeps instead of spilling them
-  double sv_g[64], sv_xl[64], sv_xe[64], sv_pl[64], sv_H[5][64];
-  double sv_f, sv_tr, sv_predv;
-  int sv_hits, sv_k, sv_status, sv_nfev;
+  // wave 0's solver state between its steps: parked here across the sweeps
+  // every wave runs, so that those registers serve the sweeps instead of
+  // spilling them
+  TrustNcgLds sv;
 };
 
 // Moments [0, a.tnl) of T slot 0 of subint c into the kernel's LDS copy
@@ -460,54 +457,7 @@ __global__ __launch_bounds__(kBlock, 3) void k_fit_taylor(FitArgs a) {
   __syncthreads();
   mark(1);
   double* acc0 = a.acc + (size_t)c * 2 * a.nchan * NACC;
-  // wave-0 solver state (lane i < 5 owns component i; scalars are uniform)
-  double f = 0.0, g = 0.0, xl = 0.0, Hrow[5] = {0, 0, 0, 0, 0};
-  double tr = 1.0, predv = 0.0, pl = 0.0;
-  int hits = 0, k = 0, status = (m.nok == 0) ? -1 : 0, nfev = 0;
-  double xe = 0.0;  // lane i < 5: the last evaluated point
-  auto save = [&] {  // wave 0
-    sh.sv_g[lane] = g;
-    sh.sv_xl[lane] = xl;
-    sh.sv_xe[lane] = xe;
-    sh.sv_pl[lane] = pl;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) sh.sv_H[j][lane] = Hrow[j];
-    if (lane == 0) {
-      sh.sv_f = f;
-      sh.sv_tr = tr;
-      sh.sv_predv = predv;
-      sh.sv_hits = hits;
-      sh.sv_k = k;
-      sh.sv_status = status;
-      sh.sv_nfev = nfev;
-    }
-  };
-  auto restore = [&] {  // wave 0, after the barrier that follows its save
-    g = sh.sv_g[lane];
-    xl = sh.sv_xl[lane];
-    xe = sh.sv_xe[lane];
-    pl = sh.sv_pl[lane];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) Hrow[j] = sh.sv_H[j][lane];
-    f = sh.sv_f;
-    tr = sh.sv_tr;
-    predv = sh.sv_predv;
-    hits = sh.sv_hits;
-    k = sh.sv_k;
-    status = sh.sv_status;
-    nfev = sh.sv_nfev;
-  };
-  if (tid < 64) save();
-  auto load_fgh = [&](double& ff, double& gg, double (&HH)[5]) {
-    ff = sh.out[0];
-    gg = lane < 5 ? sh.out[1 + lane] : 0.0;
-#pragma unroll
-    for (int p = 0; p < 15; ++p) {
-      const double v = sh.out[6 + p];
-      if (lane == pair_i(p)) HH[pair_j(p)] = v;
-      if (lane == pair_j(p)) HH[pair_i(p)] = v;
-    }
-  };
+  TrustNcg tn;  // wave 0's, in registers only within one of its steps (sh.sv)
   // the stored centre nearest p within reach (taylor_reach <= kTaylorY, the
   // first of equals), or -1; wave 0 only, no barrier
   auto pick = [&](double p0, double p1, double p2) -> int {
@@ -562,41 +512,33 @@ __global__ __launch_bounds__(kBlock, 3) void k_fit_taylor(FitArgs a) {
     mark(2);
     sweep<0, false>(a, m, c, s, sh.x, refs, P, acc0, sh.out, sh.red, source(q));
     mark(3);
-    if (tid < 64) {
-      load_fgh(f, g, Hrow);
-      xl = lane < 5 ? sh.x[lane] : 0.0;
-      xe = xl;
-      nfev = 1;
-      trace_sweep(a, s, 0, sh.x, sh.out, 21, true);
-      if (a.solver_flags & PPF_SOLVE_EVAL) {  // objective at init only
-        status = 1;
-        if (lane == 0) sh.done = 1;
-      }
-      save();
-    }
     if (tid == 0) sh.tslot = q;
+  }
+  if (tid < 64) {
+    const bool done =
+        tn.start(sh.out, sh.x, lane, m.nok, (a.solver_flags & PPF_SOLVE_EVAL) != 0);
+    if (m.nok) trace_sweep(a, s, 0, sh.x, sh.out, 21, true);
+    if (lane == 0 && done) sh.done = 1;
+    tn.park(sh.sv, lane);
   }
   __syncthreads();
   while (!sh.done) {
     if (tid < 64) {
-      restore();
-      const double jm = sqrt(dot8(g, g));
-      if (!(jm >= -1.0)) {  // NaN gradient: scipy's loop condition fails
-        status = 0;
-        if (lane == 0) sh.done = 1;
-      } else {
-        pl = steihaug(f, g, Hrow, tr, hits);
-        predv = model_val(f, g, Hrow, pl);
-        const double pv = xl + pl;  // lane i < 5: component i of the proposal
+      tn.unpark(sh.sv, lane);
+      bool same = false;
+      const bool go = tn.propose(lane, same);
+      if (go) {
+        const double pv = tn.xl + tn.pl;  // lane i < 5: component i of the proposal
         if (lane < 5) sh.xp[lane] = pv;
-        const bool same = same_point8(lane, pv, xe);
         const int qp = same ? sh.q : pick(__shfl(pv, 0), __shfl(pv, 1), __shfl(pv, 2));
         if (lane == 0) {
           sh.q = qp;
           sh.same = same;
         }
+      } else if (lane == 0) {
+        sh.done = 1;
       }
-      save();
+      tn.park(sh.sv, lane);
     }
     __syncthreads();
     mark(4);
@@ -611,53 +553,24 @@ __global__ __launch_bounds__(kBlock, 3) void k_fit_taylor(FitArgs a) {
     if (fresh) sweep<0, false>(a, m, c, s, sh.xp, refs, P, sl, sh.out, sh.red, source(q));
     mark(3);
     if (tid < 64) {
-      restore();
-      double fp, gp, Hp[5] = {0, 0, 0, 0, 0};
-      load_fgh(fp, gp, Hp);
-      if (fresh) {
-        nfev += 1;
-        xe = xl + pl;
-        trace_sweep(a, s, nfev - 1, sh.xp, sh.out, 21, true);
+      tn.unpark(sh.sv, lane);
+      bool accepted;
+      const bool done = tn.judge(sh.out, lane, fresh, accepted);
+      if (fresh) trace_sweep(a, s, tn.nfev - 1, sh.xp, sh.out, 21, true);
+      if (lane == 0) {
+        if (accepted) { sh.slot ^= 1; sh.tslot = q; }
+        if (done) sh.done = 1;
       }
-      const double actual = f - fp;
-      const double pred = f - predv;
-      if (pred <= 0.0) {
-        status = 2;
-        if (lane == 0) sh.done = 1;
-      } else {
-        const double rho = actual / pred;
-        if (rho < 0.25) tr *= 0.25;
-        else if (rho > 0.75 && hits) tr = fmin(2.0 * tr, 1000.0);
-        if (rho > 0.15) {
-          xl = xl + pl;
-          f = fp;
-          g = gp;
-#pragma unroll
-          for (int j = 0; j < 5; ++j) Hrow[j] = Hp[j];
-          if (lane == 0) { sh.slot ^= 1; sh.tslot = q; }
-          if (lane < 5) sh.x[lane] = xl;
-        }
-        k += 1;
-        if (k >= 1000) {
-          status = 1;
-          if (lane == 0) sh.done = 1;
-        }
-      }
-      save();
+      tn.park(sh.sv, lane);
     }
     __syncthreads();
   }
-  if (tid < 64) restore();
-  if (tid < 5) st.x[tid] = sh.x[tid];
-  if (tid < 5) store_grad_hess(a, s, lane, m.nok > 0, g, Hrow);
+  if (tid < 64) {
+    tn.unpark(sh.sv, lane);
+    tn.finish(a, st, s, lane, m.nok, sh.slot, false);
+  }
   if (tid == 0) {
-    st.fun = m.nok ? f : NAN;
-    st.nfev = m.nok ? nfev : 0;
-    st.status = status;
-    st.slot = sh.slot;
     st.xslot = sh.tslot;
-    st.fin = 1;
-    st.scat_post = false;
     if (prof) atomicAdd(&a.ptime[9], 1ull);
   }
 }
