@@ -33,6 +33,9 @@
  *   ppf_pca_portraits       <- pplib.pca                       pplib.py:1497-1534
  *                              (as ppspline.make_spline_model calls it,
  *                              ppspline.py:67-82, batched over portraits)
+ *   ppf_gauss_fit_batch     <- pplib.fit_gaussian_portrait     pplib.py:1924-2052
+ *                              (lmfit's leastsq, batched over portraits;
+ *                              ppf_gauss_eval is its objective)
  *   ppf_pca_project         <- pplib.reconstruct_portrait and the projection
  *                              pplib.py:1536-1553, ppspline.py:119-129
  *   ppf_synth_portraits     <- (test/bench input producer; pplib.make_fake_pulsar
@@ -107,7 +110,8 @@ extern "C" {
 #define PPF_K_RESID 13
 #define PPF_K_UNPACK 14
 #define PPF_K_PCA 15
-#define PPF_NUM_KERNELS 16
+#define PPF_K_GAUSS 16
+#define PPF_NUM_KERNELS 17
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -370,6 +374,68 @@ int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan,
 int ppf_gaussian_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin, int32_t ngauss,
                            const int32_t* code, const double* params, double nu_ref,
                            double alpha, const double* freqs, double* out);
+
+/* Gaussian-component portrait fits (fit_gaussian_portrait, pplib.py:1924-2052;
+ * ppfit_gauss.hip).  nport portraits of one shape [nchan][nbin]; everything
+ * below is DEVICE memory.  The external parameter vector of a portrait has
+ * npar = 3 + 6 ngauss entries: DC, tau [bin], per component loc, dloc, wid,
+ * dwid, amp, damp, and last the scattering index alpha.  The residual is
+ * (data - gen_gaussian_portrait(code, params[:-1], alpha, ..., freqs, nu_ref))
+ * / errs (pplib.py:1230-1242) with the portrait as ppf_gaussian_portraits
+ * builds it; errs are constant along a row ([nport][nchan], > 0).  The
+ * Jacobian is analytic (the rescale factor, the wrap and the |z| < 20
+ * support held fixed).
+ *   Limits: ngauss <= 16, nchan <= 2048, nbin a power of two in [64, 8192]
+ * (PPF_ERR_UNSUPPORTED otherwise).  Scratch is workspace
+ * (ppf_set_workspace_limit splits the call over portraits).  Results are
+ * bitwise reproducible and do not depend on how many portraits share the
+ * call.
+ *
+ * ppf_gauss_eval: at params [nport][npar], chi2[p] = |r|^2, jtr [nport][npar]
+ * = J^T r and jtj [nport][npar][npar] = J^T J with J = dr / dparams over all
+ * npar external parameters (no bounds, no step).                           */
+int ppf_gauss_eval(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                   const double* data /* [nport][nchan][nbin] */,
+                   const double* freqs /* [nport][nchan] */,
+                   const double* errs /* [nport][nchan] */,
+                   const double* params /* [nport][npar] */,
+                   const int32_t* code /* [nport][3]: loc, wid, amp; 0 power law, 1 linear */,
+                   const double* nu_ref /* [nport] */, double* chi2 /* [nport] */,
+                   double* jtr /* [nport][npar] */, double* jtj /* [nport][npar][npar] */);
+
+/* status of a Gaussian-component fit (info[p][0]) */
+#define PPF_GAUSS_FTOL 1      /* converged: MINPACK's ftol test */
+#define PPF_GAUSS_XTOL 2      /* converged: MINPACK's xtol test */
+#define PPF_GAUSS_BOTH 3      /* converged: both */
+#define PPF_GAUSS_MAXFEV 5    /* evaluation cap reached */
+#define PPF_GAUSS_SINGULAR -1 /* no step could be taken from the normal equations */
+#define PPF_GAUSS_NONFINITE -2 /* the residual at the initial point is not finite */
+
+/* ppf_gauss_fit_batch: Levenberg-Marquardt from init [nport][npar] over the
+ * parameters with flags[p][q] != 0, the rest fixed.  Bounds are lmfit's
+ * (pplib.py:1964-1988): tau >= 0, 0 <= wid <= 0.25, amp >= 0, imposed by
+ * its MINUIT transforms on internal variables (lower: val = min - 1 +
+ * sqrt(x^2 + 1); two-sided: val = min + (sin x + 1)(max - min) / 2); an
+ * initial value outside its bounds is clipped.  Each iteration solves
+ * (J^T J + lambda D^2) d = -J^T r by a Cholesky in fp64 with MINPACK's column
+ * scaling D (running maximum of the column norms, 1 for a zero column) and
+ * accepts the step by the gain ratio.  It stops by MINPACK's ftol / xtol
+ * tests (scipy.optimize.leastsq's defaults are 1.49012e-8 for both; pass
+ * them) or at max_nfev evaluations (0: 2000 (nfree + 1)).
+ *   params [nport][npar]; param_errs [nport][npar] = lmfit's stderr with
+ * scale_covar (sqrt(diag(inv(J^T J))) carried to the external values, times
+ * sqrt(chi2 / dof)), 0 for fixed parameters and for all when J^T J is
+ * singular; cov [nport][npar][npar] (may be NULL) the same covariance;
+ * chi2 [nport]; info [nport][4] = {PPF_GAUSS_* status, evaluations made,
+ * dof = nchan nbin - nfree, nfree}.  The call synchronises the stream once
+ * per iteration.                                                           */
+int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const double* data, const double* freqs, const double* errs,
+                        const double* init /* [nport][npar] */,
+                        const int32_t* flags /* [nport][npar] */, const int32_t* code,
+                        const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
+                        double* params, double* param_errs, double* cov, double* chi2,
+                        int32_t* info);
 
 /* B-spline (PCA) template rows (gen_spline_portrait, pplib.py:932-956, as
  * read_spline_model builds them, pplib.py:2961-2993): row r at freqs[r] is

@@ -20,7 +20,7 @@ METHODS = {"trust-ncg": PPF_METHOD_TRUST_NCG, "TNC": PPF_METHOD_TNC,
 KERNEL_IDS = {"model_fft": 0, "data_xspec": 1, "solve": 2, "phase_shift": 3,
               "rotate": 4, "rot_accum": 5, "synth": 6, "irfft": 7, "noise": 8,
               "guess": 9, "post": 10, "fit_taylor": 11, "moments": 12, "resid": 13, "unpack": 14,
-              "pca": 15}
+              "pca": 15, "gauss": 16}
 PPF_SOLVE_EXACT = 1
 PPF_SOLVE_EVAL = 2
 PPF_GUESS_DIRECT = 4
@@ -28,6 +28,10 @@ PPF_SPEC_NONE = 0
 PPF_SPEC_STORE = 1
 PPF_SPEC_USE = 2
 PPF_SELFTEST_N = 10
+# ppf_gauss_fit_batch status (info[p][0]) and what it means
+GAUSS_STATUS = {1: "converged: ftol", 2: "converged: xtol", 3: "converged: ftol and xtol",
+                5: "evaluation cap reached", -1: "singular normal equations",
+                -2: "non-finite residual"}
 # ppf_set_option ids (include/ppfit.h)
 OPTIONS = {"scat_graph": 0, "scat_split": 1, "scat_tail": 2, "fuse_moments": 3, "guess_wave": 4,
            "hbm_tables": 5}
@@ -128,6 +132,12 @@ EXPORTS = {
                            ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_pca_project": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                          ctypes.c_int32, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_gauss_eval": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                        ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_gauss_fit_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                             ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
+                             ctypes.c_double, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp],
+                            ctypes.c_int),
     "ppf_synth_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, ctypes.c_double,
                              ctypes.c_uint64, ctypes.c_int64, _dp], ctypes.c_int),

@@ -1657,3 +1657,196 @@ int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, co
 }
 
 }  // extern "C"
+
+namespace {
+
+// Shapes of a Gaussian-component fit and the slices of its workspace, for
+// `chunk` portraits (ppfit_gauss.hip).
+struct GaussPlan {
+  int npar, KT, KB, npairs, NH, logN;
+  int64_t chunk;
+  size_t oRows, oSpec, oDspec, oCoef, oTaun, oGram, oPext, oLm, oState, total;
+};
+
+int gauss_plan(ppf_ctx* ctx, int nport, int nchan, int nbin, int ngauss, bool fit, GaussPlan* g) {
+  if (ngauss < 1 || ngauss > kFitMaxGauss)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "ngauss=%d: 1..%d components in a fit", ngauss,
+                kFitMaxGauss);
+  if (nchan < 1 || nchan > kFitMaxChan)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: 1..%d channels in a fit", nchan, kFitMaxChan);
+  const int l = ilog2_exact(nbin);
+  if (l < 6 || nbin > 8192)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: a power of two in [64, 8192]", nbin);
+  g->logN = l - 1;
+  g->npar = 3 + 6 * ngauss;
+  g->KT = 1 + 3 * ngauss;
+  g->KB = g->KT + 2;
+  g->npairs = g->KB * (g->KB + 1) / 2;
+  g->NH = nbin / 2 + 1;
+  const size_t rows = (size_t)nchan;
+  const size_t bRows = rows * g->KT * nbin * sizeof(double);
+  const size_t bSpec = rows * g->KT * g->NH * sizeof(double2);
+  const size_t bDspec = rows * g->NH * sizeof(double2);
+  const size_t bCoef = rows * g->npar * sizeof(double), bTaun = rows * sizeof(double);
+  const size_t bGram = rows * g->npairs * sizeof(double), bPext = (size_t)g->npar * sizeof(double);
+  const size_t bLm = fit ? (size_t)kGfLmDoubles * sizeof(double) : 0;
+  const size_t per_port = bRows + bSpec + bDspec + bCoef + bTaun + bGram + bPext + bLm +
+                          sizeof(GaussFitState);
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)nport, ctx->ws_limit / (int64_t)(per_port + 4096), 65535}));
+  g->chunk = chunk;
+  const size_t c = (size_t)chunk;
+  g->oRows = 0;
+  g->oSpec = align256(g->oRows + c * bRows);
+  g->oDspec = align256(g->oSpec + c * bSpec);
+  g->oCoef = align256(g->oDspec + c * bDspec);
+  g->oTaun = align256(g->oCoef + c * bCoef);
+  g->oGram = align256(g->oTaun + c * bTaun);
+  g->oPext = align256(g->oGram + c * bGram);
+  g->oLm = align256(g->oPext + c * bPext);
+  g->oState = align256(g->oLm + c * bLm);
+  g->total = g->oState + c * sizeof(GaussFitState);
+  return PPF_OK;
+}
+
+void gauss_args(const GaussPlan& g, char* base, int nchan, int nbin, int ngauss, GaussFitArgs* a) {
+  a->nchan = nchan;
+  a->nbin = nbin;
+  a->ngauss = ngauss;
+  a->npar = g.npar;
+  a->max_nfev = 0;
+  a->fwhm = 2.0 * std::sqrt(2.0 * std::log(2.0));
+  a->sqrt2pi = std::sqrt(2.0 * M_PI);
+  a->wid_max = 0.25;
+  a->ftol = a->xtol = 0.0;
+  a->rows = reinterpret_cast<double*>(base + g.oRows);
+  a->spec = reinterpret_cast<double2*>(base + g.oSpec);
+  a->dspec = reinterpret_cast<double2*>(base + g.oDspec);
+  a->coef = reinterpret_cast<double*>(base + g.oCoef);
+  a->taun = reinterpret_cast<double*>(base + g.oTaun);
+  a->gram = reinterpret_cast<double*>(base + g.oGram);
+  a->pext = reinterpret_cast<double*>(base + g.oPext);
+  a->lm = reinterpret_cast<double*>(base + g.oLm);
+  a->state = nullptr;
+  a->flags = nullptr;
+  a->chi2 = a->jtr = a->jtj = a->params = a->perrs = a->cov = nullptr;
+  a->info = nullptr;
+}
+
+// one evaluation of np portraits at a.pext: basis rows, their spectra, the
+// per-row Gram matrices, then k_gauss_step (fit: with the solver step)
+int gauss_evaluate(ppf_ctx* ctx, const GaussPlan& g, const GaussFitArgs& a, int np, int fit,
+                   const double2* tw) {
+  return timed(ctx, PPF_K_GAUSS, [&] {
+    hipLaunchKernelGGL(k_gauss_basis, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+    launch_rfft_rows(ctx->stream, g.logN, a.nbin, np * a.nchan * g.KT, a.rows,
+                     const_cast<double2*>(a.spec), tw);
+    hipLaunchKernelGGL(k_gauss_gram, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_gauss_step, dim3(np), dim3(256), 0, ctx->stream, a, fit);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppf_gauss_eval(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                   const double* data, const double* freqs, const double* errs,
+                   const double* params, const int32_t* code, const double* nu_ref, double* chi2,
+                   double* jtr, double* jtj) {
+  if (!ctx || !data || !freqs || !errs || !params || !code || !nu_ref || !chi2 || !jtr || !jtj)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nport <= 0) return PPF_OK;
+  GaussPlan g;
+  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, false, &g)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  if (int r = ensure(ctx, ctx->buf[kWs], g.total)) return r;
+  GaussFitArgs a;
+  gauss_args(g, static_cast<char*>(ctx->buf[kWs].p), nchan, nbin, ngauss, &a);
+  for (int64_t p0 = 0; p0 < nport; p0 += g.chunk) {
+    const int np = (int)std::min<int64_t>(g.chunk, nport - p0);
+    a.freqs = freqs + (size_t)p0 * nchan;
+    a.errs = errs + (size_t)p0 * nchan;
+    a.code = code + (size_t)p0 * 3;
+    a.nu_ref = nu_ref + p0;
+    a.chi2 = chi2 + p0;
+    a.jtr = jtr + (size_t)p0 * g.npar;
+    a.jtj = jtj + (size_t)p0 * g.npar * g.npar;
+    HIPCHK(ctx, hipMemcpyAsync(a.pext, params + (size_t)p0 * g.npar,
+                               (size_t)np * g.npar * sizeof(double), hipMemcpyDeviceToDevice,
+                               ctx->stream));
+    if (int r = timed(ctx, PPF_K_GAUSS, [&] {
+          launch_rfft_rows(ctx->stream, g.logN, nbin, np * nchan,
+                           data + (size_t)p0 * nchan * nbin, const_cast<double2*>(a.dspec), tw);
+        }))
+      return r;
+    if (int r = gauss_evaluate(ctx, g, a, np, 0, tw)) return r;
+  }
+  return PPF_OK;
+}
+
+int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const double* data, const double* freqs, const double* errs,
+                        const double* init, const int32_t* flags, const int32_t* code,
+                        const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
+                        double* params, double* param_errs, double* cov, double* chi2,
+                        int32_t* info) {
+  if (!ctx || !data || !freqs || !errs || !init || !flags || !code || !nu_ref || !params ||
+      !param_errs || !chi2 || !info)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nport <= 0) return PPF_OK;
+  if (!(ftol >= 0.0) || !(xtol >= 0.0) || max_nfev < 0)
+    return fail(ctx, PPF_ERR_INVALID, "ftol=%g xtol=%g max_nfev=%d", ftol, xtol, max_nfev);
+  GaussPlan g;
+  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, true, &g)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  if (int r = ensure(ctx, ctx->buf[kWs], g.total)) return r;
+  char* base = static_cast<char*>(ctx->buf[kWs].p);
+  GaussFitArgs a;
+  gauss_args(g, base, nchan, nbin, ngauss, &a);
+  a.ftol = ftol;
+  a.xtol = xtol;
+  a.max_nfev = max_nfev;
+  a.state = reinterpret_cast<GaussFitState*>(base + g.oState);
+  std::vector<GaussFitState> hs((size_t)g.chunk);
+  const int64_t hard_cap = max_nfev > 0 ? max_nfev : 2000 * (int64_t)(g.npar + 1);
+  for (int64_t p0 = 0; p0 < nport; p0 += g.chunk) {
+    const int np = (int)std::min<int64_t>(g.chunk, nport - p0);
+    a.freqs = freqs + (size_t)p0 * nchan;
+    a.errs = errs + (size_t)p0 * nchan;
+    a.code = code + (size_t)p0 * 3;
+    a.nu_ref = nu_ref + p0;
+    a.flags = flags + (size_t)p0 * g.npar;
+    a.chi2 = chi2 + p0;
+    a.params = params + (size_t)p0 * g.npar;
+    a.perrs = param_errs + (size_t)p0 * g.npar;
+    a.cov = cov ? cov + (size_t)p0 * g.npar * g.npar : nullptr;
+    a.info = info + (size_t)p0 * 4;
+    HIPCHK(ctx, hipMemsetAsync(a.lm, 0, (size_t)np * kGfLmDoubles * sizeof(double), ctx->stream));
+    if (int r = timed(ctx, PPF_K_GAUSS, [&] {
+          launch_rfft_rows(ctx->stream, g.logN, nbin, np * nchan,
+                           data + (size_t)p0 * nchan * nbin, const_cast<double2*>(a.dspec), tw);
+          hipLaunchKernelGGL(k_gauss_init, dim3(np), dim3(256), 0, ctx->stream, a,
+                             init + (size_t)p0 * g.npar, a.flags);
+        }))
+      return r;
+    // the host reads the portraits' states once per iteration and stops when
+    // every one is done (each ends by its own cap at the latest)
+    for (int64_t it = 0; it <= hard_cap; ++it) {
+      if (int r = gauss_evaluate(ctx, g, a, np, 1, tw)) return r;
+      HIPCHK(ctx, hipMemcpyAsync(hs.data(), a.state, (size_t)np * sizeof(GaussFitState),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      bool all_done = true;
+      for (int p = 0; p < np; ++p) all_done = all_done && hs[p].done != 0;
+      if (all_done) break;
+    }
+  }
+  return PPF_OK;
+}
+
+}  // extern "C"

@@ -729,6 +729,56 @@ struct PcaState {
   double null2;   // |row|^2 at or below which a row is null in this sweep
 };
 
+// Gaussian-component portrait fits (ppfit_gauss.hip).  External parameters
+// of one portrait: DC, tau [bin], per component loc, dloc, wid, dwid, amp,
+// damp, then the scattering index alpha.
+constexpr int kFitMaxGauss = 16, kFitMaxChan = 2048;
+constexpr int kGfMaxPar = 3 + 6 * kFitMaxGauss;  // 99
+struct GaussFitState {
+  int done;    // no further iterations
+  int status;  // PPF_GAUSS_* once done
+  int nfev;    // evaluations made (the running one included)
+  int nfree;   // free parameters
+  int first;   // the running evaluation is the initial point's
+  int cap;     // evaluation cap
+  int dof;     // nchan nbin - nfree
+  int pad;
+};
+// per-portrait solver storage, in doubles: internal variables (current,
+// trial), gradients and column scales over the free parameters, scalars, and
+// the free-parameter normal matrices (current, trial)
+constexpr int kGfXi = 0, kGfXt = 100, kGfGc = 200, kGfGt = 300, kGfDg = 400, kGfSc = 500;
+constexpr int kGfHc = 520, kGfHt = kGfHc + 10000, kGfLmDoubles = kGfHt + 10000;
+constexpr int kGfChi2 = 0, kGfChi2t = 1, kGfLambda = 2, kGfNu = 3, kGfPred = 4, kGfPnorm = 5,
+              kGfXnorm = 6;
+struct GaussFitArgs {
+  int nchan, nbin, ngauss, npar;  // npar = 3 + 6 ngauss
+  int max_nfev;                   // 0: 2000 (nfree + 1)
+  double fwhm, sqrt2pi;           // 2 sqrt(2 ln 2), sqrt(2 pi) as numpy forms them
+  double wid_max, ftol, xtol;
+  const double* freqs;    // [nport][nchan]
+  const double* errs;     // [nport][nchan]
+  const int* code;        // [nport][3]
+  const double* nu_ref;   // [nport]
+  const int* flags;       // [nport][npar] (fits)
+  double* pext;           // [nport][npar] external parameters of the evaluation
+  double* rows;           // [nport][nchan][1 + 3 ngauss][nbin] time-domain rows
+  const double2* spec;    // their spectra [..][nbin / 2 + 1]
+  const double2* dspec;   // [nport][nchan][nbin / 2 + 1] data spectra
+  double* coef;           // [nport][nchan][npar] chain-rule scalars
+  double* taun;           // [nport][nchan] tau_n [rot]
+  double* gram;           // [nport][nchan][K (K + 1) / 2], K = 3 ngauss + 3
+  double* lm;             // [nport][kGfLmDoubles] (fits)
+  GaussFitState* state;   // [nport] (fits) or null
+  double* chi2;           // [nport]
+  double* jtr;            // [nport][npar] (evaluation)
+  double* jtj;            // [nport][npar][npar] (evaluation)
+  double* params;         // [nport][npar] (fits)
+  double* perrs;          // [nport][npar] (fits)
+  double* cov;            // [nport][npar][npar] or null (fits)
+  int* info;              // [nport][4] (fits)
+};
+
 constexpr int kMaxIrf = 16;
 struct IrArgs {
   int nw;                 // instrumental responses besides the DM smearing
@@ -803,6 +853,10 @@ __global__ void k_synth_gen(const double2* Mfull, const double* phase, double* d
                             int NHP, double sigma, uint64_t seed, int64_t sub0,
                             const double2* tw, int nbin);
 __global__ void k_gauss_port(GaussArgs g, const double* freqs, double* out);
+__global__ void k_gauss_basis(GaussFitArgs a);
+__global__ void k_gauss_gram(GaussFitArgs a);
+__global__ void k_gauss_init(GaussFitArgs a, const double* init, const int* flags);
+__global__ void k_gauss_step(GaussFitArgs a, int fit);
 template <typename T>
 __global__ void k_unpack(const T* raw, const double* scl, const double* offs, int nsub, int npol,
                          int nchan, int nbin, int pmode, double* out);

@@ -663,6 +663,75 @@ class Engine:
         return (proj.reshape(lead + (nchan, nc)),
                 rec.reshape(lead + (nchan, nbin)) if reconstruct else None)
 
+    def _gauss_inputs(self, data, freqs, errs, params, model_codes, nu_refs):
+        dev = self.device
+        x = _dev_f64(data, dev)
+        nchan, nbin = int(x.shape[-2]), int(x.shape[-1])
+        x = x.reshape(-1, nchan, nbin)
+        nport = int(x.shape[0])
+        f = _dev_f64(freqs, dev).reshape(-1, nchan).expand(nport, nchan).contiguous()
+        e = _dev_f64(errs, dev).reshape(-1, nchan).expand(nport, nchan).contiguous()
+        par = _dev_f64(params, dev)
+        npar = int(par.shape[-1])
+        par = par.reshape(-1, npar).expand(nport, npar).contiguous()
+        if (npar - 3) % 6 or npar < 9:
+            raise PPFitError("%d parameters: DC, tau, 6 per component and alpha" % npar)
+        if isinstance(model_codes, str):
+            model_codes = [model_codes] * nport
+        code = _dev_i32(np.array([[int(c) for c in str(mc)[:3]] for mc in model_codes],
+                                 dtype=np.int32).reshape(nport, 3), dev)
+        if ((code < 0) | (code > 1)).any():
+            raise PPFitError("model code digits are 0 (power law) or 1 (linear)")
+        nu = _dev_f64(np.broadcast_to(np.asarray(nu_refs, dtype=np.float64), (nport,)).copy(), dev)
+        return x, f, e, par, code, nu, nport, nchan, nbin, npar
+
+    def gauss_eval(self, data, freqs, errs, params, model_codes, nu_refs):
+        """chi2 [nport], J^T r [nport, npar] and J^T J [nport, npar, npar] of the
+        residual (data - gen_gaussian_portrait) / errs (pplib.py:1230-1242)
+        over the external parameters params [nport, npar] = DC, tau [bin],
+        loc, dloc, wid, dwid, amp, damp per component, alpha
+        (ppf_gauss_eval).  data [nport, nchan, nbin], freqs and errs [nport,
+        nchan].  Device tensors in, device tensors out."""
+        x, f, e, par, code, nu, nport, nchan, nbin, npar = self._gauss_inputs(
+            data, freqs, errs, params, model_codes, nu_refs)
+        dev = self.device
+        chi2 = torch.empty(nport, dtype=torch.float64, device=dev)
+        jtr = torch.empty((nport, npar), dtype=torch.float64, device=dev)
+        jtj = torch.empty((nport, npar, npar), dtype=torch.float64, device=dev)
+        self._chk(self.lib.ppf_gauss_eval(self.ctx, nport, nchan, nbin, (npar - 3) // 6, _ptr(x),
+                                          _ptr(f), _ptr(e), _ptr(par), _ptr(code), _ptr(nu),
+                                          _ptr(chi2), _ptr(jtr), _ptr(jtj)))
+        chi2._keep = (x, f, e, par, code, nu)
+        return chi2, jtr, jtj
+
+    def gauss_fit(self, data, freqs, errs, init_params, fit_flags, model_codes, nu_refs,
+                  ftol=1.49012e-8, xtol=1.49012e-8, max_nfev=0):
+        """Batched Levenberg-Marquardt fit of Gaussian-component portraits
+        (ppf_gauss_fit_batch; lmfit's leastsq of pplib.py:1924-2052 with its
+        bounds).  Shapes as gauss_eval; fit_flags [nport, npar].  Returns a
+        dict of device tensors: params, param_errs [nport, npar], cov [nport,
+        npar, npar], chi2 [nport], info [nport, 4] = status (_lib.GAUSS_STATUS),
+        evaluations, dof, nfree."""
+        x, f, e, par, code, nu, nport, nchan, nbin, npar = self._gauss_inputs(
+            data, freqs, errs, init_params, model_codes, nu_refs)
+        dev = self.device
+        fl = _dev_i32(np.broadcast_to(np.asarray(fit_flags) != 0, (nport, npar)), dev) \
+            if not isinstance(fit_flags, torch.Tensor) else \
+            (fit_flags != 0).to(device=dev, dtype=torch.int32).reshape(-1, npar).expand(
+                nport, npar).contiguous()
+        out = {"params": torch.empty((nport, npar), dtype=torch.float64, device=dev),
+               "param_errs": torch.empty((nport, npar), dtype=torch.float64, device=dev),
+               "cov": torch.empty((nport, npar, npar), dtype=torch.float64, device=dev),
+               "chi2": torch.empty(nport, dtype=torch.float64, device=dev),
+               "info": torch.zeros((nport, 4), dtype=torch.int32, device=dev)}
+        self._chk(self.lib.ppf_gauss_fit_batch(
+            self.ctx, nport, nchan, nbin, (npar - 3) // 6, _ptr(x), _ptr(f), _ptr(e), _ptr(par),
+            _ptr(fl), _ptr(code), _ptr(nu), float(ftol), float(xtol), int(max_nfev),
+            _ptr(out["params"]), _ptr(out["param_errs"]), _ptr(out["cov"]), _ptr(out["chi2"]),
+            _ptr(out["info"])))
+        out["params"]._keep = (x, f, e, par, fl, code, nu)
+        return out
+
     def _irf_call(self, nrow, nbin, rows, f, fh, DM, P, wids, irf_types, chan_bw, out):
         code = {"rect": 0, "gauss": 1}
         types = []
@@ -899,7 +968,8 @@ def _on_engine_stream(fn):
 
 
 for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portraits",
-              "spline_portraits", "pca_portraits", "pca_project", "instrumental_response_rows",
+              "spline_portraits", "pca_portraits", "pca_project", "gauss_eval", "gauss_fit",
+              "instrumental_response_rows",
               "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "spec_cache", "rotate_accumulate_spec",

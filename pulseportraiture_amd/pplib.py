@@ -246,6 +246,130 @@ def read_model_device(modelfile, nbin, freqs, P=None, quiet=False):
 
 
 # ---------------------------------------------------------------------------
+# Gaussian-component fits (ppgauss): lmfit's leastsq on the device
+# ---------------------------------------------------------------------------
+def _row_errs(errs, shape):
+    """The per-row error of the reference's errs array (one value per sample,
+    pplib.py:1945): [nchan] values when every row is constant."""
+    e = np.asarray(errs, dtype=np.float64)
+    if e.ndim == len(shape) - 1 or e.ndim == 0:
+        return np.broadcast_to(e, shape[:-1]).copy()
+    e = np.broadcast_to(e, shape)
+    if np.any(e != e[..., :1]):
+        raise NotImplementedError("errs that vary along a profile are not supported: the "
+                                  "device fit takes one error per channel")
+    return e[..., 0].copy()
+
+
+def _gauss_bunch(out, i, quiet, title):
+    from ._lib import GAUSS_STATUS
+    status, nfev, dof = (int(v) for v in out["info"][i, :3])
+    params, errs = out["params"][i], out["param_errs"][i]
+    lm = DataBunch(status=status, message=GAUSS_STATUS.get(status, "unknown"), nfev=nfev,
+                   covar=out["cov"][i], success=status in (1, 2, 3))
+    chi2 = float(out["chi2"][i])
+    if not quiet:
+        print("---------------------------------------------------------------")
+        print(title)
+        print("---------------------------------------------------------------")
+        print("status:", lm.message)
+        print("Gaussians:", (len(params) - 3) // 6)
+        print("DoF:", dof)
+        print("reduced chi-sq: %.2g" % (chi2 / dof))
+        print("---------------------------------------------------------------")
+    return DataBunch(lm_results=lm, fitted_params=params[:-1].copy(), fit_errs=errs[:-1].copy(),
+                     scattering_index=params[-1], scattering_index_err=errs[-1], chi2=chi2,
+                     dof=dof)
+
+
+def fit_gaussian_portraits(model_codes, datas, init_params, scattering_indices, errs, fit_flags,
+                           fit_scattering_indices, phases, freqs, nu_refs, join_params=[],
+                           Ps=None, quiet=True, ftol=1.49012e-8, xtol=1.49012e-8, max_nfev=0):
+    """fit_gaussian_portrait for a list of portraits of one shape in one
+    device call (ppf_gauss_fit_batch): every argument but phases is a list
+    (or an array with a leading portrait axis).  Returns a list of DataBunch."""
+    if len(join_params):
+        raise NotImplementedError("join_params (joinfile portraits) are not supported")
+    n = len(datas)
+    data = np.stack([np.asarray(d, dtype=np.float64) for d in datas])
+    if data.ndim != 3 or data.shape[-1] != len(phases):
+        raise ValueError("portraits of one shape [nchan, nbin = len(phases)] per call")
+    par = np.array([np.append(np.asarray(p, dtype=np.float64), float(a))
+                    for p, a in zip(init_params, scattering_indices)])
+    fl = np.array([np.append(np.asarray(f) != 0, bool(fa))
+                   for f, fa in zip(fit_flags, fit_scattering_indices)])
+    er = np.stack([_row_errs(e, data.shape[1:]) for e in errs])
+    out = _engine().gauss_fit(data, np.stack([np.asarray(f, dtype=np.float64) for f in freqs]),
+                              er, par, fl, [str(c) for c in model_codes],
+                              np.asarray(nu_refs, dtype=np.float64), ftol, xtol, max_nfev)
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    return [_gauss_bunch(out, i, quiet, "Gaussian Portrait Fit") for i in range(n)]
+
+
+def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
+                          fit_scattering_index, phases, freqs, nu_ref, join_params=[], P=None,
+                          quiet=True):
+    """Fit evolving Gaussian components to a portrait (pplib.py:1924-2052) on
+    the device: lmfit's leastsq with its bounds (tau >= 0, 0 <= wid <=
+    wid_max, amp >= 0) and an analytic Jacobian.  Returns the reference's
+    DataBunch; lm_results is a record of status, message, nfev, covar and
+    success.  errs [nchan, nbin] has to be constant along each row."""
+    return fit_gaussian_portraits([model_code], [data], [init_params], [scattering_index], [errs],
+                                  [fit_flags], [fit_scattering_index], phases, [freqs], [nu_ref],
+                                  join_params, None, quiet)[0]
+
+
+def profile_fit_flags(nparam, fit_flags=None, fit_scattering=False):
+    """The flags of DC, tau, (loc, wid, amp) per component from
+    fit_gaussian_profile's convention (pplib.py:1868-1873): fit_flags holds
+    DC and the component parameters, tau follows fit_scattering."""
+    if fit_flags is None:
+        flags = [True] * nparam
+        flags[1] = bool(fit_scattering)
+        return flags
+    return [bool(fit_flags[0]), bool(fit_scattering)] + [bool(fit_flags[i])
+                                                         for i in range(1, nparam - 1)]
+
+
+def fit_gaussian_profile(data, init_params, errs, fit_flags=None, fit_scattering=False,
+                         quiet=True):
+    """Fit Gaussian components to a profile (pplib.py:1842-1922): the
+    portrait solver with one channel at freq = nu_ref and the evolution
+    parameters fixed at 0 under the linear code, where the value is the
+    parameter exactly.  Returns fitted_params, fit_errs, residuals, chi2, dof."""
+    data = np.asarray(data, dtype=np.float64)
+    init_params = np.asarray(init_params, dtype=np.float64)
+    nparam = len(init_params)
+    ngauss = (nparam - 2) // 3
+    flags = profile_fit_flags(nparam, fit_flags, fit_scattering)
+    par, fl = np.zeros(2 + 6 * ngauss), np.zeros(2 + 6 * ngauss, dtype=bool)
+    par[:2], fl[:2] = init_params[:2], flags[:2]
+    for k in range(3):
+        par[2 + 2 * k::6], fl[2 + 2 * k::6] = init_params[2 + k::3], flags[2 + k::3]
+    e = _row_errs((np.asarray(errs, dtype=np.float64) + np.zeros(len(data)))[None],
+                  (1, len(data)))
+    fgp = fit_gaussian_portraits(["111"], [data[None]], [par], [0.0], [e], [fl], [False],
+                                 get_bin_centers(len(data)), [np.ones(1)], [1.0], quiet=True)[0]
+    keep = np.sort(np.concatenate([[0, 1]] + [np.arange(2 + 2 * k, len(par), 6)
+                                             for k in range(3)])).astype(int)
+    fitted, fit_errs = fgp.fitted_params[keep], fgp.fit_errs[keep]
+    residuals = data - gen_gaussian_profile(fitted, len(data))
+    if not quiet:
+        print("---------------------------------------------------------------")
+        print("Multi-Gaussian Profile Fit Results")
+        print("---------------------------------------------------------------")
+        print("status:", fgp.lm_results.message)
+        print("Gaussians:", ngauss)
+        print("DoF:", fgp.dof)
+        print("reduced chi-sq: %.2f" % (fgp.chi2 / fgp.dof))
+        print("residuals mean: %.3g" % np.mean(residuals))
+        print("residuals std.: %.3g" % np.std(residuals))
+        print("---------------------------------------------------------------")
+    return DataBunch(fitted_params=fitted, fit_errs=fit_errs, residuals=residuals, chi2=fgp.chi2,
+                     dof=fgp.dof, lm_results=fgp.lm_results)
+
+
+# ---------------------------------------------------------------------------
 # B-spline (PCA) templates: ppspline.py models (host reader, device builder)
 # ---------------------------------------------------------------------------
 class _SplineUnpickler(pickle.Unpickler):
