@@ -40,6 +40,13 @@
  *                              pplib.py:1536-1553, ppspline.py:119-129
  *   ppf_synth_portraits     <- (test/bench input producer; pplib.make_fake_pulsar
  *                              math, pplib.py:3342-3377, on device)
+ *   ppf_fake_subints        <- pplib.make_fake_pulsar's data  pplib.py:3342-3379
+ *                              (every polarisation, amplitude and noise level,
+ *                              as 16-bit PSRFITS samples)
+ *   ppf_pack_subints        <- PSRCHIVE's unload of amplitudes as 16-bit samples
+ *                              in write_archive / unload_new_archive
+ *                              pplib.py:3039-3187 (with include/ppfitsw.h, the
+ *                              host PSRFITS writer)
  *
  * Conventions
  *  - Every array argument is a DEVICE pointer (hipMalloc'd or a torch CUDA
@@ -64,7 +71,8 @@
  *    ppf_resid_chi2_rows run direct-sum kernels instead (O(nbin^2) per row;
  *    tests/test_gpu_generic_nbin.py), and so do the data-spectrum cache
  *    (PPF_SPEC_*, ppf_spec_nhp, ppf_rotate_accumulate_spec) and
- *    ppf_synth_portraits: every entry point takes any nbin in [16, 8192]
+ *    ppf_synth_portraits, ppf_fake_subints and ppf_pack_subints: every
+ *    entry point takes any nbin in [16, 8192]
  *    (powers of two below 64 take the generic kernels too).
  *  - Channel counts: up to PPF_LDS_NCHAN a fit workgroup keeps its subint's
  *    per-channel tables (frequencies, weights, dispersion derivatives, the
@@ -111,7 +119,8 @@ extern "C" {
 #define PPF_K_UNPACK 14
 #define PPF_K_PCA 15
 #define PPF_K_GAUSS 16
-#define PPF_NUM_KERNELS 17
+#define PPF_K_PACK 17
+#define PPF_NUM_KERNELS 18
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -157,6 +166,7 @@ int ppf_set_option(ppf_ctx* ctx, int32_t option, int32_t value);
 int ppf_get_option(const ppf_ctx* ctx, int32_t option, int32_t* value);
 /* Upper bound on workspace bytes the context may hold (default 32 GiB). */
 int ppf_set_workspace_limit(ppf_ctx* ctx, int64_t bytes);
+int ppf_get_workspace_limit(const ppf_ctx* ctx, int64_t* bytes);
 /* Per-kernel HIP-event timing on the context stream (off by default). */
 int ppf_set_timing(ppf_ctx* ctx, int enable);
 /* Diagnostic: record every objective sweep of the TNC and Newton-CG solvers
@@ -544,6 +554,41 @@ int ppf_noise_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,
 int ppf_synth_portraits(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
                         const double* model, const double* phase, double sigma,
                         uint64_t seed, int64_t sub0, double* data);
+
+/* fp64 values to 16-bit PSRFITS samples, the inverse of ppf_unpack_subints:
+ * data [nsub][npol][nchan][nbin] -> raw (int16, native byte order) with scl
+ * and offs [nsub][npol][nchan], value ~ raw * scl + offs.  Per row, with lo
+ * and hi its exact minimum and maximum:
+ *   offs = (float)(0.5 (lo + hi))
+ *   scl  = the smallest float32 >= max(hi - offs, offs - lo) / 32767 (fp64)
+ *   raw  = rint((x - offs) / scl) in fp64, ties to even
+ * so |raw| <= 32767 without a clamp and |raw scl + offs - x| <= scl / 2 up
+ * to fp64 rounding.  scl and offs are fp64 values exactly representable in
+ * float32 (the file stores them as E).  A constant row takes scl = 1, offs =
+ * (float)lo, raw = 0.  A row with a non-finite sample is stored as zeros
+ * (scl 1, offs 0) and the call returns PPF_ERR_INVALID.  The call waits for
+ * the stream (it returns that status).                                     */
+int ppf_pack_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                     const double* data, int16_t* raw, double* scl, double* offs);
+
+/* ppf_synth_portraits with polarisations, amplitudes and per-channel noise:
+ * data[s][p][n] = amp[s][n] irfft(rfft(model[n]) e^{2 pi i k phase[s][n]})
+ *                 + sigma[n] N(0,1)[Philox4x32-10(seed; bin pair,
+ *                                                  n + nchan p, s + sub0)]
+ * model [nchan][nbin], phase and amp [nsub][nchan], sigma [nchan].  The
+ * result does not depend on how the subints are split into calls (sub0);
+ * with npol = 1, amp = 1 and one sigma it is bitwise ppf_synth_portraits'.
+ * Output, one of:
+ *   data [nsub][npol][nchan][nbin] fp64 (raw, scl, offs NULL; no wait), or
+ *   raw, scl, offs (data NULL): those rows quantised exactly as
+ *   ppf_pack_subints quantises them, its status and its wait included.  For
+ *   a power-of-two nbin >= 64 one kernel makes and quantises each row in
+ *   LDS, so 2 bytes per sample reach HBM; other nbin write the fp64 rows to
+ *   workspace (PPF_ERR_NOMEM above the workspace limit) and pack them.    */
+int ppf_fake_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                     const double* model, const double* phase, const double* amp,
+                     const double* sigma, uint64_t seed, int64_t sub0, double* data, int16_t* raw,
+                     double* scl, double* offs);
 
 #ifdef __cplusplus
 }

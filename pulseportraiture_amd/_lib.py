@@ -20,7 +20,7 @@ METHODS = {"trust-ncg": PPF_METHOD_TRUST_NCG, "TNC": PPF_METHOD_TNC,
 KERNEL_IDS = {"model_fft": 0, "data_xspec": 1, "solve": 2, "phase_shift": 3,
               "rotate": 4, "rot_accum": 5, "synth": 6, "irfft": 7, "noise": 8,
               "guess": 9, "post": 10, "fit_taylor": 11, "moments": 12, "resid": 13, "unpack": 14,
-              "pca": 15, "gauss": 16}
+              "pca": 15, "gauss": 16, "pack": 17}
 PPF_SOLVE_EXACT = 1
 PPF_SOLVE_EVAL = 2
 PPF_GUESS_DIRECT = 4
@@ -76,6 +76,7 @@ EXPORTS = {
     "ppf_synchronize": ([ctypes.c_void_p], ctypes.c_int),
     "ppf_set_pipeline": ([ctypes.c_void_p, ctypes.c_int32], ctypes.c_int),
     "ppf_set_workspace_limit": ([ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
+    "ppf_get_workspace_limit": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "ppf_set_timing": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "ppf_set_trace": ([ctypes.c_void_p, _dp, ctypes.c_int32], ctypes.c_int),
     "ppf_set_option": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
@@ -141,6 +142,11 @@ EXPORTS = {
     "ppf_synth_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, ctypes.c_double,
                              ctypes.c_uint64, ctypes.c_int64, _dp], ctypes.c_int),
+    "ppf_pack_subints": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                          ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_fake_subints": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                          ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.c_uint64, ctypes.c_int64,
+                          _dp, _dp, _dp, _dp], ctypes.c_int),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 """Build the in-tree libraries (no CUDA, no JIT cache):
 
 - libppfit.so  -- the HIP library (hipcc, gfx950), include/ppfit.h;
-- libppfits.so -- the host PSRFITS reader (g++), include/ppfits.h;
+- libppfits.so -- the host PSRFITS reader and writer (g++), include/ppfits.h
+  and include/ppfitsw.h;
 - libpptim.so  -- the host .tim writer (g++), include/pptim.h.
 
 Each library carries the sha256 of its sources, headers and compile command
@@ -24,8 +25,8 @@ CXX = os.environ.get("CXX", "g++")
 
 SOURCES = ["ppfit_lib.hip"]
 DEPS = ["ppfit_lib.hip", "ppfit_spectra.hip", "ppfit_fit.hip", "ppfit_taylor.hip", "ppfit_tnc.hip",
-        "ppfit_ncg.hip", "ppfit_models.hip", "ppfit_generic.hip", "ppfit_pca.hip", "ppfit_gauss.hip",
-        "ppfit_capi.hip", "ppfit_kernels.hpp", "ppfit_device.hpp"]
+        "ppfit_ncg.hip", "ppfit_models.hip", "ppfit_generic.hip", "ppfit_fake.hip", "ppfit_pca.hip",
+        "ppfit_gauss.hip", "ppfit_capi.hip", "ppfit_kernels.hpp", "ppfit_device.hpp"]
 OUT = os.path.join(HERE, "libppfit.so")
 FITS_OUT = os.path.join(HERE, "libppfits.so")
 TIM_OUT = os.path.join(HERE, "libpptim.so")
@@ -39,8 +40,9 @@ def _lib_specs():
             "-I" + CSRC, os.path.join(CSRC, SOURCES[0])],
            [os.path.join(CSRC, f) for f in DEPS] + [os.path.join(INC, "ppfit.h")])
     fits = ([CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + INC,
-             os.path.join(CSRC, "psrfits.cpp")],
-            [os.path.join(CSRC, "psrfits.cpp"), os.path.join(INC, "ppfits.h")])
+             os.path.join(CSRC, "psrfits.cpp"), os.path.join(CSRC, "psrfits_write.cpp")],
+            [os.path.join(CSRC, "psrfits.cpp"), os.path.join(CSRC, "psrfits_write.cpp"),
+             os.path.join(INC, "ppfits.h"), os.path.join(INC, "ppfitsw.h")])
     tim = ([CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread", "-I" + INC,
             os.path.join(CSRC, "pptim.cpp")],
            [os.path.join(CSRC, "pptim.cpp"), os.path.join(INC, "pptim.h")])

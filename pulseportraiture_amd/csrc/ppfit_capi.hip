@@ -45,6 +45,7 @@ enum BufferId {
   kPtime,  // k_fit_taylor phase clocks (ppf_phase_profile)
   kSpart,  // split scattering solve: block partials + running count
   kTmpl,   // template builders: knots / coefficients, rows and spectra
+  kPack,   // pack status word, then ppf_fake_subints' fp64 rows (generic nbin)
   kNumBuffers
 };
 
@@ -745,6 +746,36 @@ int fit_tables(ppf_ctx* ctx, const ppf_fit_desc* d, SpecArgs& sa, FitArgs& fa) {
   return PPF_OK;
 }
 
+// ---------------------------------------------------------------------------
+// ppf_pack_subints / ppf_fake_subints: the status word of the packing kernels
+// ---------------------------------------------------------------------------
+constexpr size_t kPackHead = 256;  // the status word's slice of buf[kPack]
+
+// Zero the pack status word (buf[kPack] holds kPackHead + extra bytes).
+int pack_begin(ppf_ctx* ctx, size_t extra, int** bad) {
+  if (int r = ensure(ctx, ctx->buf[kPack], kPackHead + extra)) return r;
+  *bad = static_cast<int*>(ctx->buf[kPack].p);
+  HIPCHK(ctx, hipMemsetAsync(*bad, 0, sizeof(int), ctx->stream));
+  return PPF_OK;
+}
+
+// Wait for the packing kernels and read the status word.
+int pack_end(ppf_ctx* ctx, const int* bad) {
+  int h = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (h) return fail(ctx, PPF_ERR_INVALID, "non-finite sample: its row is stored as zeros");
+  return PPF_OK;
+}
+
+int launch_pack(ppf_ctx* ctx, size_t rows, int nbin, const double* data, int16_t* raw, double* scl,
+                double* offs, int* bad) {
+  return timed(ctx, PPF_K_PACK, [&] {
+    hipLaunchKernelGGL(k_pack, dim3((unsigned)rows), dim3(kBlock), 0, ctx->stream, data, nbin,
+                       reinterpret_cast<short*>(raw), scl, offs, bad);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -822,6 +853,12 @@ int ppf_synchronize(ppf_ctx* ctx) {
 int ppf_set_workspace_limit(ppf_ctx* ctx, int64_t bytes) {
   if (!ctx || bytes <= 0) return PPF_ERR_INVALID;
   ctx->ws_limit = bytes;
+  return PPF_OK;
+}
+
+int ppf_get_workspace_limit(const ppf_ctx* ctx, int64_t* bytes) {
+  if (!ctx || !bytes) return PPF_ERR_INVALID;
+  *bytes = ctx->ws_limit;
   return PPF_OK;
 }
 
@@ -1311,6 +1348,85 @@ int ppf_synth_portraits(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
                                          ctx->stream, M, phase, data, nchan, NHP, sigma, seed,
                                          sub0, tw));
   });
+}
+
+int ppf_pack_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                     const double* data, int16_t* raw, double* scl, double* offs) {
+  if (!ctx || !data || !raw || !scl || !offs) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nsub <= 0) return PPF_OK;
+  if (npol <= 0 || nchan <= 0) return fail(ctx, PPF_ERR_INVALID, "bad shape");
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  const size_t rows = (size_t)nsub * npol * nchan;
+  if (rows > 0x7fffffffULL) return fail(ctx, PPF_ERR_INVALID, "%zu profiles in one call", rows);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int* bad;
+  if (int r = pack_begin(ctx, 0, &bad)) return r;
+  if (int r = launch_pack(ctx, rows, nbin, data, raw, scl, offs, bad)) return r;
+  return pack_end(ctx, bad);
+}
+
+int ppf_fake_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                     const double* model, const double* phase, const double* amp,
+                     const double* sigma, uint64_t seed, int64_t sub0, double* data, int16_t* raw,
+                     double* scl, double* offs) {
+  if (!ctx || !model || !phase || !amp || !sigma) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  const bool pack = data == nullptr;
+  if (pack ? (!raw || !scl || !offs) : (raw || scl || offs))
+    return fail(ctx, PPF_ERR_INVALID, "pass data, or raw with scl and offs");
+  if (nsub <= 0) return PPF_OK;
+  if (npol <= 0 || nchan <= 0 || (int64_t)npol * nchan > 0x7fffffff)
+    return fail(ctx, PPF_ERR_INVALID, "bad shape");
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  const size_t rows = (size_t)nsub * npol * nchan;
+  if (rows > 0x7fffffffULL) return fail(ctx, PPF_ERR_INVALID, "%zu profiles in one call", rows);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  double2* M;
+  double* pn;
+  if (int r = model_spectra(ctx, nchan, nbin, model, 0, ctx->buf[kAux], &M, &pn)) return r;
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  FakeArgs a{};
+  a.M = M;
+  a.phase = phase;
+  a.amp = amp;
+  a.sigma = sigma;
+  a.npol = npol;
+  a.nchan = nchan;
+  a.NHP = nharm_pad(nbin);
+  a.seed = seed;
+  a.sub0 = sub0;
+  a.data = data;
+  a.raw = reinterpret_cast<short*>(raw);
+  a.scl = scl;
+  a.offs = offs;
+  const bool fused = pack && logN >= 0;
+  if (pack) {
+    // generic nbin: the fp64 rows go through the workspace, then k_pack
+    const size_t rbytes = fused ? 0 : rows * (size_t)nbin * sizeof(double);
+    if ((int64_t)rbytes > ctx->ws_limit)
+      return fail(ctx, PPF_ERR_NOMEM, "%zu bytes of rows exceed the workspace limit", rbytes);
+    if (int r = pack_begin(ctx, rbytes, &a.bad)) return r;
+    if (!fused) a.data = reinterpret_cast<double*>(static_cast<char*>(ctx->buf[kPack].p) + kPackHead);
+  }
+  if (int r = timed(ctx, PPF_K_SYNTH, [&] {
+        if (logN < 0) {
+          hipLaunchKernelGGL(k_fake_gen, dim3((unsigned)rows), dim3(kBlock), gen_spec_lds(nbin),
+                             ctx->stream, a, tw, nbin);
+        } else if (fused) {
+          LOGN_SWITCH(logN, hipLaunchKernelGGL((k_fake<LG, true>), dim3((unsigned)rows),
+                                               dim3(kBlock), 0, ctx->stream, a, tw));
+        } else {
+          LOGN_SWITCH(logN, hipLaunchKernelGGL((k_fake<LG, false>), dim3((unsigned)rows),
+                                               dim3(kBlock), 0, ctx->stream, a, tw));
+        }
+      }))
+    return r;
+  if (!pack) return PPF_OK;
+  if (!fused)
+    if (int r = launch_pack(ctx, rows, nbin, a.data, raw, scl, offs, a.bad)) return r;
+  return pack_end(ctx, a.bad);
 }
 
 int ppf_rotate_accumulate(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,

@@ -852,6 +852,25 @@ __global__ void k_data_post_gen(SpecArgs a, int nbin);
 __global__ void k_synth_gen(const double2* Mfull, const double* phase, double* data, int nchan,
                             int NHP, double sigma, uint64_t seed, int64_t sub0,
                             const double2* tw, int nbin);
+// ppf_fake_subints / ppf_pack_subints (ppfit_fake.hip)
+struct FakeArgs {
+  const double2* M;     // model spectra [nchan][NHP]
+  const double* phase;  // [nsub][nchan]
+  const double* amp;    // [nsub][nchan]
+  const double* sigma;  // [nchan]
+  int npol, nchan, NHP;
+  uint64_t seed;
+  int64_t sub0;
+  double* data;         // fp64 rows [nsub][npol][nchan][nbin], or
+  short* raw;           // their int16 samples with
+  double* scl;          // [nsub][npol][nchan]
+  double* offs;
+  int* bad;             // set to 1 by a row with a non-finite sample
+};
+template <int LOGN, bool PACK> __global__ void k_fake(FakeArgs a, const double2* tw);
+__global__ void k_fake_gen(FakeArgs a, const double2* tw, int nbin);
+__global__ void k_pack(const double* data, int nbin, short* raw, double* scl, double* offs,
+                       int* bad);
 __global__ void k_gauss_port(GaussArgs g, const double* freqs, double* out);
 __global__ void k_gauss_basis(GaussFitArgs a);
 __global__ void k_gauss_gram(GaussFitArgs a);

@@ -475,10 +475,12 @@ __global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a) {
 struct C2rPlain {
   __device__ double2 operator()(int, double2 v) const { return v; }
 };
-template <int LOGN, typename Epi = C2rPlain>
-__device__ void c2r_from_spectrum(double2* buf, double2 (&xs)[((1 << LOGN) + kBlock) / kBlock + 1],
-                                  const double2* __restrict__ tw, double* __restrict__ out,
-                                  Epi epi = Epi()) {
+// The transform alone: buf[j] (j in [0, N)) is left holding N times the sample
+// pair (2j, 2j + 1); the caller synchronises nothing more before reading its
+// own j = tid + i kBlock.
+template <int LOGN>
+__device__ void c2r_in_lds(double2* buf, double2 (&xs)[((1 << LOGN) + kBlock) / kBlock + 1],
+                           const double2* __restrict__ tw) {
   constexpr int N = 1 << LOGN;
   constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
   const int tid = threadIdx.x;
@@ -507,9 +509,17 @@ __device__ void c2r_from_spectrum(double2* buf, double2 (&xs)[((1 << LOGN) + kBl
   }
   __syncthreads();
   lds_fft<LOGN, true>(buf, tw);
+}
+
+template <int LOGN, typename Epi = C2rPlain>
+__device__ void c2r_from_spectrum(double2* buf, double2 (&xs)[((1 << LOGN) + kBlock) / kBlock + 1],
+                                  const double2* __restrict__ tw, double* __restrict__ out,
+                                  Epi epi = Epi()) {
+  constexpr int N = 1 << LOGN;
+  c2r_in_lds<LOGN>(buf, xs, tw);
   const double inv = 1.0 / (double)N;
   double2* o2 = reinterpret_cast<double2*>(out);
-  for (int j = tid; j < N; j += kBlock) o2[j] = epi(j, cscale(buf[j], inv));
+  for (int j = threadIdx.x; j < N; j += kBlock) o2[j] = epi(j, cscale(buf[j], inv));
 }
 
 template <int LOGN>

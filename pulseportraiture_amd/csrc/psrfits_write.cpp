@@ -1,0 +1,372 @@
+// psrfits_write.cpp -- streaming fold-mode PSRFITS writer behind
+// include/ppfitsw.h (the layout psrfits.cpp reads; see its opening comment).
+//
+// HDU order: primary, HISTORY (one row), PSRPARAM (one row per ephemeris
+// line), SUBINT.  SUBINT is last so rows can be appended until ppfw_close,
+// which then rewrites the two cells that hold the subint count (SUBINT's
+// NAXIS2 card, HISTORY's NSUB) and pads the data to a FITS block.
+#include "ppfitsw.h"
+
+#include <cerrno>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ppfits.h"
+
+namespace {
+
+constexpr size_t kBlock = 2880;
+constexpr size_t kCard = 80;
+constexpr size_t kParamWidth = 128;  // PSRPARAM's PARAM column, 128A
+
+bool be_host() {
+  const uint16_t x = 1;
+  return *reinterpret_cast<const uint8_t*>(&x) == 0;
+}
+
+// width bytes of src (native order) to dst in big-endian order
+void put_be(uint8_t* dst, const void* src, size_t width) {
+  const uint8_t* s = static_cast<const uint8_t*>(src);
+  if (be_host()) {
+    memcpy(dst, s, width);
+    return;
+  }
+  for (size_t i = 0; i < width; ++i) dst[i] = s[width - 1 - i];
+}
+void put_f64(uint8_t* dst, double v) { put_be(dst, &v, 8); }
+void put_f32(uint8_t* dst, double v) { const float f = (float)v; put_be(dst, &f, 4); }
+void put_i32(uint8_t* dst, int32_t v) { put_be(dst, &v, 4); }
+void put_i16(uint8_t* dst, int16_t v) { put_be(dst, &v, 2); }
+
+// n int16 samples to big-endian order
+void put_i16_row(uint8_t* dst, const int16_t* src, size_t n) {
+  if (be_host()) {
+    memcpy(dst, src, 2 * n);
+    return;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const uint16_t v = (uint16_t)src[i];
+    dst[2 * i] = (uint8_t)(v >> 8);
+    dst[2 * i + 1] = (uint8_t)v;
+  }
+}
+
+// A FITS header under construction: 80-character cards.
+struct Header {
+  std::string txt;
+
+  void raw(const std::string& key, const std::string& value, const char* comment) {
+    std::string c = key;
+    c.resize(8, ' ');
+    c += "= " + value;
+    if (comment && *comment && c.size() + 3 < kCard) c += std::string(" / ") + comment;
+    c.resize(kCard, ' ');
+    txt += c;
+  }
+  void str(const char* key, const std::string& v, const char* comment = "") {
+    std::string q;
+    for (char ch : v) {
+      if (ch == '\'') q += "''"; else q += (ch >= 32 && ch < 127) ? ch : ' ';
+    }
+    if (q.size() > 66) q.resize(66);
+    if (q.size() < 8) q.resize(8, ' ');
+    std::string val = "'" + q + "'";
+    if (val.size() < 20) val.resize(20, ' ');
+    raw(key, val, comment);
+  }
+  void right(const char* key, const std::string& v, const char* comment) {
+    raw(key, v.size() < 20 ? std::string(20 - v.size(), ' ') + v : v, comment);
+  }
+  void integer(const char* key, long long v, const char* comment = "") {
+    right(key, std::to_string(v), comment);
+  }
+  void logical(const char* key, bool v, const char* comment = "") {
+    right(key, v ? "T" : "F", comment);
+  }
+  void real(const char* key, double v, const char* comment = "") {
+    char b[40];
+    snprintf(b, sizeof b, "%.17G", v);
+    std::string s = b;
+    if (std::isfinite(v) && s.find_first_of(".E") == std::string::npos) s += ".0";
+    right(key, s, comment);
+  }
+  // the finished header: END card, blank-padded to a block
+  std::string done() const {
+    std::string out = txt + "END";
+    out.resize((out.size() + kBlock - 1) / kBlock * kBlock, ' ');
+    return out;
+  }
+  // byte offset of key's card in the header (it must be there)
+  size_t find(const char* key) const {
+    std::string k = key;
+    k.resize(8, ' ');
+    for (size_t c = 0; c < txt.size(); c += kCard)
+      if (txt.compare(c, 8, k) == 0) return c;
+    return std::string::npos;
+  }
+};
+
+struct Col {
+  const char* name;
+  long repeat;
+  char type;
+  const char* unit;
+};
+
+size_t type_width(char t) {
+  switch (t) {
+    case 'A': return 1;
+    case 'I': return 2;
+    case 'J': case 'E': return 4;
+    default: return 8;  // 'D'
+  }
+}
+
+// the header of a binary table of nrows rows (cols in row order)
+Header table_header(const char* extname, const std::vector<Col>& cols, size_t nrows) {
+  size_t row = 0;
+  for (const Col& c : cols) row += type_width(c.type) * (size_t)c.repeat;
+  Header h;
+  h.str("XTENSION", "BINTABLE", "binary table extension");
+  h.integer("BITPIX", 8);
+  h.integer("NAXIS", 2);
+  h.integer("NAXIS1", (long long)row, "bytes per row");
+  h.integer("NAXIS2", (long long)nrows, "rows");
+  h.integer("PCOUNT", 0);
+  h.integer("GCOUNT", 1);
+  h.integer("TFIELDS", (long long)cols.size());
+  for (size_t i = 0; i < cols.size(); ++i) {
+    const std::string n = std::to_string(i + 1);
+    h.str(("TTYPE" + n).c_str(), cols[i].name);
+    h.str(("TFORM" + n).c_str(), std::to_string(cols[i].repeat) + cols[i].type);
+    if (cols[i].unit && *cols[i].unit) h.str(("TUNIT" + n).c_str(), cols[i].unit);
+  }
+  h.str("EXTNAME", extname);
+  return h;
+}
+
+std::string field(const char* s, size_t cap) {  // a desc string, NUL-terminated or full
+  return std::string(s, strnlen(s, cap));
+}
+
+}  // namespace
+
+struct ppfw_file {
+  FILE* fp = nullptr;
+  std::string err;
+  int status = PPFITS_OK;
+  ppfw_desc d{};
+  int32_t nsub = 0;
+  size_t naxis2_off = 0;   // SUBINT's NAXIS2 card
+  size_t hist_nsub_off = 0;  // HISTORY's NSUB cell
+  size_t row_bytes = 0;
+  std::vector<uint8_t> row;
+
+  int fail(int code, const std::string& msg) {
+    if (status == PPFITS_OK) { status = code; err = msg; }
+    return code;
+  }
+  bool put(const void* p, size_t n) { return fwrite(p, 1, n, fp) == n; }
+  bool pad(size_t bytes) {  // zero fill of a data unit to a block
+    const std::vector<uint8_t> z((kBlock - bytes % kBlock) % kBlock, 0);
+    return z.empty() || put(z.data(), z.size());
+  }
+
+  int write_head(const char* ephemeris) {
+    const ppfw_desc& D = d;
+    Header p;
+    p.logical("SIMPLE", true, "file conforms to FITS");
+    p.integer("BITPIX", 8);
+    p.integer("NAXIS", 0);
+    p.logical("EXTEND", true);
+    p.str("HDRVER", "6.1", "PSRFITS header version");
+    p.str("FITSTYPE", "PSRFITS", "FITS definition for pulsar data files");
+    p.str("TELESCOP", field(D.telescope, sizeof D.telescope));
+    p.str("FRONTEND", field(D.frontend, sizeof D.frontend));
+    p.str("BACKEND", field(D.backend, sizeof D.backend));
+    p.real("BE_DELAY", D.be_delay, "[s] backend delay");
+    p.str("OBS_MODE", "PSR", "folded pulsar data");
+    p.str("SRC_NAME", field(D.source, sizeof D.source));
+    p.str("COORD_MD", "J2000");
+    p.real("EQUINOX", 2000.0);
+    p.str("RA", field(D.ra, sizeof D.ra), "hh:mm:ss.ssss");
+    p.str("DEC", field(D.dec, sizeof D.dec), "-dd:mm:ss.sss");
+    p.str("STT_CRD1", field(D.ra, sizeof D.ra));
+    p.str("STT_CRD2", field(D.dec, sizeof D.dec));
+    p.real("OBSFREQ", D.obsfreq, "[MHz] centre frequency");
+    p.real("OBSBW", D.obsbw, "[MHz] bandwidth");
+    p.integer("OBSNCHAN", D.nchan);
+    p.real("CHAN_DM", D.dm, "[cm-3 pc]");
+    p.integer("STT_IMJD", D.stt_imjd, "start MJD");
+    p.integer("STT_SMJD", D.stt_smjd, "[s] start second of the day");
+    p.real("STT_OFFS", D.stt_offs, "[s] start fractional second");
+    std::string out = p.done();
+
+    // HISTORY: one row, the state the data are stored in
+    const double chan_bw = D.obsbw / (double)D.nchan;
+    const std::vector<Col> hc = {{"DATE_PRO", 24, 'A', ""}, {"PROC_CMD", 80, 'A', ""},
+                                 {"SCALE", 8, 'A', ""}, {"POL_TYPE", 8, 'A', ""},
+                                 {"NSUB", 1, 'J', ""}, {"NPOL", 1, 'I', ""},
+                                 {"NBIN", 1, 'I', ""}, {"NBIN_PRD", 1, 'I', ""},
+                                 {"TBIN", 1, 'D', "s"}, {"CTR_FREQ", 1, 'D', "MHz"},
+                                 {"NCHAN", 1, 'J', ""}, {"CHAN_BW", 1, 'D', "MHz"},
+                                 {"DM", 1, 'D', "CM-3 PC"}, {"RM", 1, 'D', "RAD M-2"},
+                                 {"PR_CORR", 1, 'I', ""}, {"FD_CORR", 1, 'I', ""},
+                                 {"BE_CORR", 1, 'I', ""}, {"RM_CORR", 1, 'I', ""},
+                                 {"DEDISP", 1, 'I', ""}};
+    out += table_header("HISTORY", hc, 1).done();
+    std::vector<uint8_t> hr;
+    auto text = [&](const std::string& s, size_t w) {
+      std::string t = s;
+      t.resize(w, ' ');
+      hr.insert(hr.end(), t.begin(), t.end());
+    };
+    auto num = [&](char type, double v) {
+      uint8_t b[8];
+      if (type == 'D') put_f64(b, v);
+      else if (type == 'J') put_i32(b, (int32_t)v);
+      else put_i16(b, (int16_t)v);
+      hr.insert(hr.end(), b, b + type_width(type));
+    };
+    text("", 24);
+    text("pulseportraiture_amd write_archive", 80);
+    text("FluxDen", 8);
+    text(field(D.pol_type, sizeof D.pol_type), 8);
+    hist_nsub_off = out.size() + hr.size();
+    num('J', 0);
+    num('I', D.npol);
+    num('I', D.nbin);
+    num('I', D.nbin);
+    num('D', 0.0);
+    num('D', D.obsfreq);
+    num('J', D.nchan);
+    num('D', chan_bw);
+    num('D', D.dm);
+    num('D', 0.0);
+    for (int i = 0; i < 4; ++i) num('I', 0);
+    num('I', D.dedispersed ? 1 : 0);
+    out.append(reinterpret_cast<const char*>(hr.data()), hr.size());
+    out.append((kBlock - hr.size() % kBlock) % kBlock, '\0');
+
+    // PSRPARAM: the ephemeris, one line per row
+    std::vector<std::string> lines;
+    for (const char* s = ephemeris ? ephemeris : ""; *s;) {
+      const char* e = strchr(s, '\n');
+      std::string ln = e ? std::string(s, e - s) : std::string(s);
+      while (!ln.empty() && (ln.back() == '\r' || ln.back() == ' ')) ln.pop_back();
+      if (!ln.empty()) lines.push_back(ln);
+      if (!e) break;
+      s = e + 1;
+    }
+    out += table_header("PSRPARAM", {{"PARAM", (long)kParamWidth, 'A', ""}}, lines.size()).done();
+    const size_t pbytes = lines.size() * kParamWidth;
+    for (std::string ln : lines) {
+      ln.resize(kParamWidth, ' ');
+      out += ln;
+    }
+    out.append((kBlock - pbytes % kBlock) % kBlock, '\0');
+
+    // SUBINT
+    const long pc = (long)D.npol * D.nchan;
+    const std::vector<Col> sc = {{"TSUBINT", 1, 'D', "s"}, {"OFFS_SUB", 1, 'D', "s"},
+                                 {"PERIOD", 1, 'D', "s"}, {"PAR_ANG", 1, 'E', "deg"},
+                                 {"DAT_FREQ", D.nchan, 'D', "MHz"}, {"DAT_WTS", D.nchan, 'E', ""},
+                                 {"DAT_OFFS", pc, 'E', ""}, {"DAT_SCL", pc, 'E', ""},
+                                 {"DATA", pc * D.nbin, 'I', "Jy"}};
+    Header s = table_header("SUBINT", sc, 0);
+    char tdim[64];
+    snprintf(tdim, sizeof tdim, "(%d,%d,%d)", D.nbin, D.nchan, D.npol);
+    s.str(("TDIM" + std::to_string(sc.size())).c_str(), tdim, "(NBIN,NCHAN,NPOL)");
+    s.str("INT_TYPE", "TIME");
+    s.str("INT_UNIT", "SEC");
+    s.str("SCALE", "FluxDen");
+    s.integer("NPOL", D.npol);
+    s.str("POL_TYPE", field(D.pol_type, sizeof D.pol_type));
+    s.integer("NBIN", D.nbin);
+    s.integer("NBIN_PRD", D.nbin);
+    s.real("PHS_OFFS", 0.0);
+    s.integer("NBITS", 1);
+    s.integer("NCHAN", D.nchan);
+    s.real("CHAN_BW", chan_bw, "[MHz]");
+    s.real("DM", D.dm, "[cm-3 pc]");
+    s.real("RM", 0.0, "[rad m-2]");
+    s.integer("NSBLK", 1);
+    naxis2_off = out.size() + s.find("NAXIS2");
+    out += s.done();
+    row_bytes = 8 * 3 + 4 + (size_t)D.nchan * 12 + (size_t)pc * 8 + (size_t)pc * D.nbin * 2;
+    row.resize(row_bytes);
+    if (!put(out.data(), out.size())) return fail(PPFITS_ERR_IO, "header write failed");
+    return PPFITS_OK;
+  }
+};
+
+extern "C" {
+
+int ppfw_create(const char* path, const ppfw_desc* desc, const char* ephemeris, ppfw_file** out) {
+  if (!path || !desc || !out) return PPFITS_ERR_IO;
+  ppfw_file* f = new ppfw_file();
+  *out = f;
+  f->d = *desc;
+  if (desc->npol < 1 || desc->nchan < 1 || desc->nbin < 1 ||
+      (double)desc->npol * desc->nchan * desc->nbin > 2147483647.0)
+    return f->fail(PPFITS_ERR_FORMAT, "bad shape (npol, nchan, nbin)");
+  f->fp = fopen(path, "wb");
+  if (!f->fp) return f->fail(PPFITS_ERR_IO, std::string("cannot create ") + path + ": " + strerror(errno));
+  return f->write_head(ephemeris);
+}
+
+int ppfw_write_subints(ppfw_file* f, int32_t isub0, int32_t n, const int16_t* raw,
+                       const double* scl, const double* offs, const double* freqs,
+                       const double* wts, const double* tsubint, const double* offs_sub,
+                       const double* period, const double* par_ang) {
+  if (!f) return PPFITS_ERR_IO;
+  if (!f->fp || f->status != PPFITS_OK) return f->fail(PPFITS_ERR_IO, "file is not open for writing");
+  if (n < 0 || isub0 != f->nsub)
+    return f->fail(PPFITS_ERR_RANGE, "subints must be appended in order: expected isub0 = " +
+                                         std::to_string(f->nsub));
+  if (n && (!raw || !scl || !offs || !freqs || !wts || !tsubint || !offs_sub || !period))
+    return f->fail(PPFITS_ERR_MISSING, "null array");
+  const size_t nchan = (size_t)f->d.nchan, pc = (size_t)f->d.npol * nchan;
+  const size_t nsamp = pc * (size_t)f->d.nbin;
+  for (int32_t r = 0; r < n; ++r) {
+    uint8_t* o = f->row.data();
+    put_f64(o, tsubint[r]); o += 8;
+    put_f64(o, offs_sub[r]); o += 8;
+    put_f64(o, period[r]); o += 8;
+    put_f32(o, par_ang ? par_ang[r] : 0.0); o += 4;
+    for (size_t i = 0; i < nchan; ++i, o += 8) put_f64(o, freqs[r * nchan + i]);
+    for (size_t i = 0; i < nchan; ++i, o += 4) put_f32(o, wts[r * nchan + i]);
+    for (size_t i = 0; i < pc; ++i, o += 4) put_f32(o, offs[r * pc + i]);
+    for (size_t i = 0; i < pc; ++i, o += 4) put_f32(o, scl[r * pc + i]);
+    put_i16_row(o, raw + (size_t)r * nsamp, nsamp);
+    if (!f->put(f->row.data(), f->row_bytes)) return f->fail(PPFITS_ERR_IO, "SUBINT write failed");
+    f->nsub += 1;
+  }
+  return PPFITS_OK;
+}
+
+int ppfw_close(ppfw_file* f) {
+  if (!f) return PPFITS_ERR_IO;
+  if (f->fp && f->status == PPFITS_OK && f->row_bytes) {
+    bool ok = f->pad((size_t)f->nsub * f->row_bytes);
+    Header h;
+    h.integer("NAXIS2", f->nsub, "rows");
+    uint8_t nb[4];
+    put_i32(nb, f->nsub);
+    ok = ok && fseeko(f->fp, (off_t)f->naxis2_off, SEEK_SET) == 0 && f->put(h.txt.data(), kCard);
+    ok = ok && fseeko(f->fp, (off_t)f->hist_nsub_off, SEEK_SET) == 0 && f->put(nb, 4);
+    if (!ok) f->fail(PPFITS_ERR_IO, "finishing the file failed");
+  }
+  if (f->fp && fclose(f->fp) != 0) f->fail(PPFITS_ERR_IO, "close failed");
+  f->fp = nullptr;
+  const int rc = f->status;
+  delete f;
+  return rc;
+}
+
+const char* ppfw_error(const ppfw_file* f) { return f ? f->err.c_str() : "null file"; }
+
+}  // extern "C"

@@ -950,6 +950,59 @@ class Engine:
         out._keep = (m, ph)
         return out
 
+    def pack_subints(self, data):
+        """fp64 values [nsub, npol, nchan, nbin] to 16-bit PSRFITS samples on
+        the device (ppf_pack_subints, the inverse of unpack_subints): returns
+        (raw int16 [nsub, npol, nchan, nbin], scl, offs [nsub, npol, nchan]).
+        A non-finite sample raises PPFitError."""
+        d = _dev_f64(data, self.device)
+        if d.dim() != 4:
+            raise PPFitError("pack_subints: data [nsub, npol, nchan, nbin]")
+        nsub, npol, nchan, nbin = d.shape
+        raw = torch.empty(d.shape, dtype=torch.int16, device=self.device)
+        scl = torch.empty((nsub, npol, nchan), dtype=torch.float64, device=self.device)
+        offs = torch.empty_like(scl)
+        self._chk(self.lib.ppf_pack_subints(self.ctx, nsub, npol, nchan, nbin, _ptr(d), _ptr(raw),
+                                            _ptr(scl), _ptr(offs)))
+        return raw, scl, offs
+
+    def fake_subints(self, model, phase, amp, sigma, seed, sub0=0, npol=1, packed=False):
+        """Fake-pulsar subints on the device (ppf_fake_subints): model [nchan,
+        nbin], phase / amp [nsub, nchan] (amp: anything that broadcasts),
+        sigma [nchan] or a scalar.  Returns data [nsub, npol, nchan, nbin]
+        float64, or with packed=True its 16-bit samples (raw, scl, offs) as
+        pack_subints gives them."""
+        dev = self.device
+        m = _dev_f64(model, dev)
+        nchan, nbin = m.shape
+        ph = _dev_f64(phase, dev)
+        nsub = ph.numel() // nchan
+        ph = ph.reshape(nsub, nchan).contiguous()
+        a = _dev_f64(amp, dev).broadcast_to(nsub, nchan).contiguous()
+        sg = _dev_f64(sigma, dev).broadcast_to(nchan).contiguous()
+        shape = (nsub, npol, nchan, nbin)
+        data = raw = scl = offs = None
+        if packed:
+            raw = torch.empty(shape, dtype=torch.int16, device=dev)
+            scl = torch.empty(shape[:3], dtype=torch.float64, device=dev)
+            offs = torch.empty_like(scl)
+        else:
+            data = torch.empty(shape, dtype=torch.float64, device=dev)
+        self._chk(self.lib.ppf_fake_subints(self.ctx, nsub, int(npol), nchan, nbin, _ptr(m),
+                                            _ptr(ph), _ptr(a), _ptr(sg),
+                                            int(seed) & (2 ** 64 - 1), int(sub0), _ptr(data),
+                                            _ptr(raw), _ptr(scl), _ptr(offs)))
+        if packed:
+            return raw, scl, offs  # the call has waited for the stream
+        data._keep = (m, ph, a, sg)
+        return data
+
+    def workspace_limit(self):
+        """The device workspace cap in bytes (ppf_get_workspace_limit)."""
+        n = ctypes.c_int64()
+        self._chk(self.lib.ppf_get_workspace_limit(self.ctx, ctypes.byref(n)))
+        return n.value
+
 
 def _on_engine_stream(fn):
     """Run an Engine call with its stream current: the temporaries it makes
@@ -973,7 +1026,7 @@ for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portrai
               "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "spec_cache", "rotate_accumulate_spec",
-              "synth"):
+              "synth", "pack_subints", "fake_subints"):
     setattr(Engine, _name, _on_engine_stream(getattr(Engine, _name)))
 del _name
 

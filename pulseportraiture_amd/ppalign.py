@@ -663,8 +663,11 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
     """Iteratively align and average archives; returns aligned_port[npol, nchan, nbin].
 
     The reference writes the result into a PSRCHIVE archive; here the portrait
-    is returned (and written with archive.save_archive when ``outfile`` ends in
-    .npz).  ``timings`` (diagnostic): a dict that receives the wall time of
+    is returned, and rank 0 writes it as a PSRFITS file when ``outfile`` ends
+    in .fits (the default ``<metafile>.algnd.fits`` for a metafile: one
+    dedispersed subint with the initial guess's metadata, DM 0 and weights 1
+    or 0, pplib.unload_new_archive) or with archive.save_archive when it ends
+    in .npz.  ``timings`` (diagnostic): a dict that receives the wall time of
     each phase (open, unit stack, per-iteration fit / accumulate / exchange),
     with a device synchronisation at every phase boundary.
     """
@@ -768,6 +771,14 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False, pscrunc
         _arch.save_archive(outfile, dict(subints=aligned[None], freqs=model_data.freqs[0],
                                          Ps=model_data.Ps[:1], epochs=model_data.epochs[:1],
                                          weights=w[None], DM=0.0))
+    elif outfile is not None and str(outfile).endswith(".fits") and rank == 0:
+        # the averaged archive (ppalign.py:227-243): the initial guess's
+        # metadata, tscrunched, one dedispersed subint with DM 0
+        from .pplib import unload_new_archive
+        w = np.where(tw.cpu().numpy() > 0, 1.0, 0.0)
+        meta = {k: v for k, v in model_data.items() if k != "subints"}
+        unload_new_archive(aligned[None], meta, outfile, DM=0.0, dmc=1, weights=w[None],
+                           quiet=quiet)
     if return_weights:
         return aligned, tw.cpu().numpy()
     return aligned

@@ -742,6 +742,292 @@ def fit_portrait(data, model, init_params, P, freqs, nu_fit=None, nu_out=None, e
 
 
 # ---------------------------------------------------------------------------
+# Fake data and archive output (pplib.py:1146-1174, 2509-2546, 3039-3384):
+# PSRFITS files written by psrfits.PSRFITSWriter from 16-bit samples that
+# the device packs (ppf_pack_subints) or generates (ppf_fake_subints)
+# ---------------------------------------------------------------------------
+def _scint_pattern(nchan, params=None, nsin=2, amax=1.0, wmax=3.0, rng=None):
+    """add_scintillation's per-channel pattern (pplib.py:1159-1173); rng: a
+    numpy Generator for the random parameters (None: numpy's global state)."""
+    rng = np.random if rng is None else rng
+    if params is None:
+        params = []
+        for _ in range(nsin):
+            params += [rng.uniform(0, amax), rng.chisquare(wmax), rng.uniform(0, 1)]
+    pattern = np.zeros(nchan)
+    for isin in range(len(params) // 3):
+        a, w, p = params[isin * 3:isin * 3 + 3]
+        pattern += a * np.sin(np.linspace(0, w * np.pi, nchan) + p * np.pi) ** 2
+    return pattern
+
+
+def add_scintillation(port, params=None, random=True, nsin=2, amax=1.0, wmax=3.0, rng=None):
+    """pplib.py:1146-1174 (host numpy); rng: see _scint_pattern."""
+    port = np.asarray(port, dtype=np.float64)
+    if params is None and random is False:
+        return port
+    return port * _scint_pattern(len(port), params, nsin, amax, wmax, rng)[:, None]
+
+
+def _DM_nu_term(freqs, xs, Cs, nu_ref):
+    """add_DM_nu's frequency term sum_i C_i (nu**x_i - nu_ref**x_i), pplib.py:2536-2542."""
+    if not hasattr(Cs, "__iter__"):
+        Cs = np.ones(len(xs))
+    Cs = list(Cs) + [1.0] * (len(xs) - len(Cs))
+    freqs = np.asarray(freqs, dtype=np.float64)
+    term = np.zeros(freqs.shape)
+    for C, x in zip(Cs, xs):
+        term = term + C * (freqs ** x - nu_ref ** x)
+    return term
+
+
+def add_DM_nu(port, phase=0.0, DM=None, P=None, freqs=None, xs=[-2.0], Cs=[1.0], nu_ref=np.inf):
+    """pplib.py:2509-2546 (host numpy)."""
+    port = np.asarray(port, dtype=np.float64)
+    pFFT = np.fft.rfft(port, axis=1)
+    k = np.arange(pFFT.shape[1])
+    if DM is None and freqs is None:
+        rot = np.full(len(port), float(phase))
+    else:
+        rot = phase + Dconst * DM / P * _DM_nu_term(freqs, xs, Cs, nu_ref)
+    return np.fft.irfft(pFFT * np.exp(2.0j * np.pi * rot[:, None] * k), port.shape[1], axis=1)
+
+
+def read_ephemeris(ephemeris):
+    """The fields write_archive and make_fake_pulsar take from a parameter
+    file, by the reference's own parse (pplib.py:3133-3147, 3284-3302): PSR
+    or PSRJ, RAJ, DECJ, DM, F0 or P0, PEPOCH; plus the file's text."""
+    with open(ephemeris, "r") as fh:
+        text = fh.read()
+    par = DataBunch(PSR="noname", RAJ="00:00:00.0", DECJ="+00:00:00.0", DM=0.0, P0=None,
+                    PEPOCH=None, text=text)
+    for line in text.splitlines():
+        f = line.split()
+        if len(f) < 2:
+            continue
+        if f[0] in ("PSR", "PSRJ"):
+            par.PSR = f[1]
+        elif f[0] in ("RAJ", "DECJ"):
+            par[f[0]] = f[1]
+        elif f[0] == "F0":
+            par.P0 = np.float64(f[1].replace("D", "E")) ** -1
+        elif f[0] in ("P0", "PEPOCH", "DM"):
+            par[f[0]] = np.float64(f[1].replace("D", "E"))
+    if par.DECJ[0] not in "+-":
+        par.DECJ = "+" + par.DECJ
+    return par
+
+
+def _as_MJD(x, default):
+    from .mjd import MJD
+    if x is None:
+        x = default
+    return x if isinstance(x, MJD) else MJD(x)
+
+
+def _chunk_subints(eng, npol, nchan, nbin):
+    """Subints per chunk of an archive being written: a chunk's fp64 rows and
+    int16 samples within the engine's workspace limit, and at most 1 GiB so
+    that the host writes one chunk while the device makes the next."""
+    budget = min(eng.workspace_limit(), 1 << 30)
+    return max(1, budget // (10 * npol * nchan * nbin))
+
+
+def _write_chunks(w, nsub, chunk, make, freqs, weights, tsubint, offs_sub, period, par_ang):
+    """make(lo, hi) -> device (raw, scl, offs) of subints lo:hi, appended to
+    the writer w; the previous chunk is written (a thread in the C writer)
+    while the device makes this one."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(1) as pool:
+        pending = None
+        for lo in range(0, nsub, chunk):
+            hi = min(nsub, lo + chunk)
+            raw, scl, offs = (t.cpu().numpy() for t in make(lo, hi))
+            if pending is not None:
+                pending.result()
+            pending = pool.submit(w.write, raw, scl, offs, freqs[lo:hi], weights[lo:hi],
+                                  tsubint[lo:hi], offs_sub[lo:hi], period[lo:hi], par_ang[lo:hi])
+        if pending is not None:
+            pending.result()
+
+
+def _unload(outfile, data, meta, rot=None):
+    """Write data [nsub, npol, nchan, nbin] (host array or device tensor) as a
+    PSRFITS file: per chunk, optionally rotated by rot [nsub, nchan] [rot],
+    packed on the device and appended.  meta: PSRFITSWriter's keywords plus
+    freqs, weights [nsub, nchan] and tsubint, offs_sub, period, par_ang [nsub]."""
+    import torch
+    from .psrfits import PSRFITSWriter
+    eng = _engine()
+    nsub, npol, nchan, nbin = tuple(data.shape)
+    meta = dict(meta)
+    rows = [np.asarray(meta.pop(k), dtype=np.float64) for k in
+            ("freqs", "weights", "tsubint", "offs_sub", "period", "par_ang")]
+
+    def make(lo, hi):
+        d = data[lo:hi]
+        if isinstance(d, torch.Tensor):
+            d = d.to(device=eng.device, dtype=torch.float64).contiguous()
+            if rot is not None and d.data_ptr() == data[lo:hi].data_ptr():
+                d = d.clone()  # the caller's tensor is not rotated
+        else:
+            d = torch.as_tensor(np.ascontiguousarray(d, dtype=np.float64), device=eng.device)
+        if rot is not None:
+            eng.rotate_rows(d, np.repeat(rot[lo:hi, None, :], npol, axis=1), inplace=True)
+        return eng.pack_subints(d)
+
+    with PSRFITSWriter(outfile, npol, nchan, nbin, **meta) as w:
+        _write_chunks(w, nsub, _chunk_subints(eng, npol, nchan, nbin), make, *rows)
+
+
+def write_archive(data, ephemeris, freqs, nu0=None, bw=None, outfile="pparchive.fits", tsub=1.0,
+                  start_MJD=None, weights=None, dedispersed=False, state="Stokes",
+                  telescope="GBT", quiet=False):
+    """pplib.py:3077-3187 without PSRCHIVE: a fold-mode PSRFITS file written
+    by the package (psrfits.PSRFITSWriter, 16-bit samples packed on the
+    device).  data [nsub, npol, nchan, nbin], a host array or a device
+    tensor, is taken dedispersed; with dedispersed=False it is stored
+    rotated to the dispersed state by the ephemeris DM about nu0, the
+    rotation load_data(..., dedisperse=True) undoes
+    (archive.dedispersion_phases).  The ephemeris parse is read_ephemeris;
+    the period (1 / F0 or P0) is constant and goes into the PERIOD column,
+    there are no polycos.  Epochs are start_MJD + tsub / 2 + i tsub;
+    start_MJD is an mjd.MJD or a float [day] (None: MJD 50000)."""
+    from .archive import dedispersion_phases
+    nsub, npol, nchan, nbin = tuple(data.shape)
+    freqs = np.asarray(freqs, dtype=np.float64)
+    if nu0 is None:
+        nu0 = freqs.mean()
+    if bw is None:
+        bw = (freqs.max() - freqs.min()) + abs(freqs[1] - freqs[0])
+    par = read_ephemeris(ephemeris)
+    if par.P0 is None:
+        raise ValueError("%s has neither F0 nor P0" % ephemeris)
+    Ps = np.full(nsub, float(par.P0))
+    fr = np.tile(freqs, (nsub, 1))
+    rot = None if dedispersed else -dedispersion_phases(fr, Ps, float(par.DM), float(nu0))
+    meta = dict(start=_as_MJD(start_MJD, 50000.0), nu0=nu0, bw=bw, DM=par.DM,
+                dedispersed=dedispersed, state=state, telescope=telescope, source=par.PSR,
+                ra=par.RAJ, dec=par.DECJ, ephemeris=par.text, freqs=fr,
+                weights=np.ones((nsub, nchan)) if weights is None else weights,
+                tsubint=np.full(nsub, float(tsub)), offs_sub=tsub / 2.0 + tsub * np.arange(nsub),
+                period=Ps, par_ang=np.zeros(nsub))
+    _unload(outfile, data, meta, rot)
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
+
+
+def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None, quiet=False):
+    """pplib.py:3039-3075 without PSRCHIVE: data [nsub, npol, nchan, nbin]
+    (host array or device tensor, in the state dmc says) written as a PSRFITS
+    file with the metadata of arch -- a load_data bunch, or the name of an
+    archive load_data reads.  DM and weights replace arch's when given.
+    Epochs are stored as offsets from the first epoch's whole second."""
+    from . import archive as _archive
+    if isinstance(arch, str):
+        arch = _archive.open_archive(arch, rm_baseline=False).meta
+    b = _archive.normalize(arch, str(outfile), subints="subints" in arch)
+    nsub, npol, nchan, nbin = tuple(data.shape)
+    if (nsub, nchan, nbin) != (b.nsub, b.nchan, b.nbin):
+        raise ValueError("data %s does not fit the archive (%d, npol, %d, %d)" % (
+            tuple(data.shape), b.nsub, b.nchan, b.nbin))
+    e0 = b.epochs[0]
+    offs_sub = np.array([(e.days - e0.days) * 86400.0 + (e.secs - e0.secs) + e.fracsec
+                         for e in b.epochs])
+    from .mjd import MJD
+    meta = dict(start=MJD(e0.days, e0.secs, 0.0), nu0=b.nu0, bw=b.bw,
+                DM=b.DM if DM is None else DM, dedispersed=bool(dmc), state=b.state,
+                telescope=b.telescope, frontend=b.frontend, backend=b.backend,
+                backend_delay=b.backend_delay, source=b.source, freqs=b.freqs,
+                weights=b.weights if weights is None else weights, tsubint=b.subtimes,
+                offs_sub=offs_sub, period=b.Ps, par_ang=b.parallactic_angles)
+    _unload(outfile, data, meta)
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
+
+
+def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.fits", nsub=1, npol=1, nchan=512,
+                     nbin=2048, nu0=1500.0, bw=800.0, tsub=300.0, phase=0.0, dDM=0.0,
+                     start_MJD=None, weights=None, noise_stds=1.0, scales=1.0, dedispersed=False,
+                     t_scat=0.0, alpha=scattering_alpha, scint=False, xs=None, Cs=None,
+                     nu_DM=np.inf, state="Stokes", telescope="GBT", quiet=False, seed=None):
+    """pplib.py:3189-3384 without PSRCHIVE: fake pulsar data generated on
+    the device (ppf_fake_subints: the model rows of read_model_device, one
+    rotation, amplitude and Philox noise stream per profile, quantised to
+    16-bit samples as they are made) and written as a PSRFITS file in chunks.
+    Arguments are the reference's; the folding period is the ephemeris's
+    constant 1 / F0 (or P0), and every polarisation holds the same model with
+    its own noise.  seed (None: fresh entropy) fixes the noise and, with
+    scint=True, the scintillation pattern drawn per subint from a
+    numpy.random.Generator.
+
+    Two deliberate deviations from the reference's HEAD:
+    - phase and dDM act when xs is None too, as rotate_data(model, -phase,
+      -dDM, P, freqs, nu0); the reference ignores them there
+      (pplib.py:3347-3349), against its own docstring;
+    - phase and dDM may each be an array of length nsub (one per subint).
+    """
+    from .archive import dedispersion_phases
+    chanwidth = bw / nchan
+    lofreq = nu0 - (bw / 2)
+    freqs = np.linspace(lofreq + (chanwidth / 2.0), lofreq + bw - (chanwidth / 2.0), nchan)
+    noise_stds = np.asarray(noise_stds, dtype=np.float64)
+    if noise_stds.ndim and len(noise_stds) != nchan:
+        print("\nlen(noise_stds) != nchan\n")
+        return 0
+    scales = np.asarray(scales, dtype=np.float64)
+    if scales.ndim and len(scales) != nchan:
+        print("\nlen(scales) != nchan\n")
+        return 0
+    par = read_ephemeris(ephemeris)
+    if par.P0 is None:
+        raise ValueError("%s has neither F0 nor P0" % ephemeris)
+    P, DM = float(par.P0), float(par.DM)
+    start = _as_MJD(start_MJD, par.PEPOCH if par.PEPOCH is not None else 50000.0)
+    tau_model = read_model(modelfile, quiet=True)[4][1]
+    name, ngauss, model = read_model_device(modelfile, nbin, freqs, P, quiet=True)
+    if t_scat and not tau_model:  # modelfile overrides
+        taus = scattering_times(t_scat / P, alpha, freqs, nu0)
+        model = _engine().scatter_rotate_rows(model, 0.0, taus)
+    # every rotation of a profile in one phase [rot]
+    ph = np.ones(nsub) * phase
+    dDMs = np.ones(nsub) * dDM
+    if xs is None:
+        term = freqs ** -2.0 - nu0 ** -2.0
+    else:
+        ph = phase_transform(ph, DM + dDMs, nu0, nu_DM, P)
+        term = _DM_nu_term(freqs, xs, Cs, nu_DM)
+    rot = -ph[:, None] - (Dconst * dDMs / P)[:, None] * term[None, :]
+    Ps = np.full(nsub, P)
+    fr = np.tile(freqs, (nsub, 1))
+    if not dedispersed:
+        rot = rot - dedispersion_phases(fr, Ps, DM, nu0)
+    rng = np.random.default_rng(seed)
+    amp = np.ones((nsub, nchan)) * scales
+    if scint is not False:
+        for isub in range(nsub):
+            amp[isub] *= _scint_pattern(nchan, nsin=3, amax=1.0, wmax=5.0, rng=rng) \
+                if scint is True else _scint_pattern(nchan, scint)
+    noise_seed = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
+    eng = _engine()
+
+    def make(lo, hi):
+        return eng.fake_subints(model, rot[lo:hi], amp[lo:hi], noise_stds, noise_seed, sub0=lo,
+                                npol=npol, packed=True)
+
+    from .psrfits import PSRFITSWriter
+    with PSRFITSWriter(outfile, npol, nchan, nbin, start, nu0, bw, DM=DM,
+                       dedispersed=dedispersed, state=state, telescope=telescope,
+                       source=par.PSR, ra=par.RAJ, dec=par.DECJ, ephemeris=par.text) as w:
+        _write_chunks(w, nsub, _chunk_subints(eng, npol, nchan, nbin), make, fr,
+                      np.ones((nsub, nchan)) if weights is None else np.asarray(weights, float),
+                      np.full(nsub, float(tsub)), tsub / 2.0 + tsub * np.arange(nsub), Ps,
+                      np.zeros(nsub))
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
+
+
+# ---------------------------------------------------------------------------
 # TOA output (pplib.py:3386-3509)
 # ---------------------------------------------------------------------------
 def filter_TOAs(TOAs, flag, cutoff, criterion=">=", pass_unflagged=False,

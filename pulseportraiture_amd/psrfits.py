@@ -1,4 +1,4 @@
-"""PSRFITS archives for load_data.
+"""PSRFITS archives for load_data, and their writer.
 
 ``PSRFITSSource`` is the archive.Archive source for a fold-mode PSRFITS
 file: the host reader ``libppfits.so`` (include/ppfits.h, plain C++) parses
@@ -15,6 +15,11 @@ them from the ephemeris and observatory), channel S/N 1 (Profile.snr()
 weights only guess_fit_freq's reference frequency).  The folding period is
 the SUBINT PERIOD column when present, else the POLYCO predictor's frequency
 at the subint epoch; the DEDISP flag of the last HISTORY row is ``dmc``.
+
+``PSRFITSWriter`` is the other direction (include/ppfitsw.h, the same
+library): pplib.write_archive, unload_new_archive and make_fake_pulsar hand
+it 16-bit samples the device packed (``ppf_pack_subints``) or generated
+(``ppf_fake_subints``), chunk by chunk.
 """
 import ctypes
 import os
@@ -58,6 +63,22 @@ class _Info(ctypes.Structure):
                 ("pol_type", ctypes.c_char * 16), ("obs_mode", ctypes.c_char * 16)]
 
 
+class _WDesc(ctypes.Structure):
+    """ppfw_desc (include/ppfitsw.h)."""
+    _fields_ = [("npol", ctypes.c_int32), ("nchan", ctypes.c_int32), ("nbin", ctypes.c_int32),
+                ("dedispersed", ctypes.c_int32), ("stt_imjd", ctypes.c_int32),
+                ("stt_smjd", ctypes.c_int32), ("stt_offs", ctypes.c_double),
+                ("obsfreq", ctypes.c_double), ("obsbw", ctypes.c_double),
+                ("dm", ctypes.c_double), ("be_delay", ctypes.c_double),
+                ("telescope", ctypes.c_char * 32), ("frontend", ctypes.c_char * 32),
+                ("backend", ctypes.c_char * 32), ("source", ctypes.c_char * 32),
+                ("pol_type", ctypes.c_char * 16), ("ra", ctypes.c_char * 32),
+                ("dec", ctypes.c_char * 32)]
+
+
+# POL_TYPE of a PSRCHIVE polarisation state (write_archive's `state`)
+POL_TYPES = {"STOKES": "IQUV", "COHERENCE": "AABBCRCI", "PPQQ": "AABB", "INTENSITY": "AA+BB"}
+
 _lib = None
 
 
@@ -84,6 +105,16 @@ def load_library():
     lib.ppfits_read_raw.restype = ctypes.c_int
     lib.ppfits_read_polyco.argtypes = [vp] + [dp] * 5
     lib.ppfits_read_polyco.restype = ctypes.c_int
+    # the writer (include/ppfitsw.h)
+    lib.ppfw_create.argtypes = [ctypes.c_char_p, ctypes.POINTER(_WDesc), ctypes.c_char_p,
+                                ctypes.POINTER(vp)]
+    lib.ppfw_create.restype = ctypes.c_int
+    lib.ppfw_write_subints.argtypes = [vp, ctypes.c_int32, ctypes.c_int32] + [dp] * 9
+    lib.ppfw_write_subints.restype = ctypes.c_int
+    lib.ppfw_close.argtypes = [vp]
+    lib.ppfw_close.restype = ctypes.c_int
+    lib.ppfw_error.argtypes = [vp]
+    lib.ppfw_error.restype = ctypes.c_char_p
     _lib = lib
     return lib
 
@@ -152,6 +183,80 @@ class PSRFITSFile:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class PSRFITSWriter:
+    """A fold-mode PSRFITS archive being written (include/ppfitsw.h): the
+    headers, HISTORY and PSRPARAM tables at creation, then SUBINT rows
+    appended in chunks by write(), the row counts fixed by close().
+
+    start: the MJD the OFFS_SUB column counts from; state: PSRCHIVE's
+    polarisation state ("Intensity", "Stokes", "Coherence", "PPQQ") or a
+    POL_TYPE itself; ephemeris: the parameter file's text."""
+
+    def __init__(self, path, npol, nchan, nbin, start, nu0, bw, DM=0.0, dedispersed=False,
+                 state="Intensity", telescope="GBT", frontend="unknown", backend="unknown",
+                 backend_delay=0.0, source="noname", ra="00:00:00.0", dec="+00:00:00.0",
+                 ephemeris=""):
+        self.lib = load_library()
+        self.path = path
+        self.npol, self.nchan, self.nbin = int(npol), int(nchan), int(nbin)
+        self.nsub = 0
+        d = _WDesc()
+        d.npol, d.nchan, d.nbin = self.npol, self.nchan, self.nbin
+        d.dedispersed = int(bool(dedispersed))
+        d.stt_imjd, d.stt_smjd, d.stt_offs = int(start.days), int(start.secs), float(start.fracsec)
+        d.obsfreq, d.obsbw, d.dm, d.be_delay = float(nu0), float(bw), float(DM), float(backend_delay)
+        pol = "AA+BB" if self.npol == 1 else POL_TYPES.get(str(state).upper(), str(state))
+        for k, v, n in (("telescope", telescope, 32), ("frontend", frontend, 32),
+                        ("backend", backend, 32), ("source", source, 32), ("pol_type", pol, 16),
+                        ("ra", ra, 32), ("dec", dec, 32)):
+            setattr(d, k, str(v).encode("ascii", "replace")[:n - 1])
+        self.h = ctypes.c_void_p()
+        rc = self.lib.ppfw_create(os.fsencode(path), ctypes.byref(d),
+                                  str(ephemeris).encode("ascii", "replace"), ctypes.byref(self.h))
+        if rc != 0:
+            msg = self.lib.ppfw_error(self.h).decode() if self.h else "create failed"
+            self.close(check=False)
+            raise PSRFITSError("%s: %s" % (path, msg))
+
+    def write(self, raw, scl, offs, freqs, wts, tsubint, offs_sub, period, par_ang=None):
+        """Append len(raw) subints: raw [n, npol, nchan, nbin] int16, scl /
+        offs [n, npol, nchan], freqs / wts [n, nchan], the rest [n]."""
+        raw = np.ascontiguousarray(raw, dtype=np.int16)
+        n = raw.shape[0]
+        if raw.shape != (n, self.npol, self.nchan, self.nbin):
+            raise PSRFITSError("%s: raw %s is not [n, %d, %d, %d]" % (
+                self.path, raw.shape, self.npol, self.nchan, self.nbin))
+        shapes = [(n, self.npol, self.nchan)] * 2 + [(n, self.nchan)] * 2 + [(n,)] * 4
+        arrs = []
+        for a, sh in zip((scl, offs, freqs, wts, tsubint, offs_sub, period, par_ang), shapes):
+            if a is not None:
+                a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), sh))
+            arrs.append(a)
+        rc = self.lib.ppfw_write_subints(self.h, self.nsub, n, _p(raw), *[_p(a) for a in arrs])
+        if rc != 0:
+            raise PSRFITSError("%s: %s" % (self.path, self.lib.ppfw_error(self.h).decode()))
+        self.nsub += n
+
+    def close(self, check=True):
+        if getattr(self, "h", None):
+            rc = self.lib.ppfw_close(self.h)
+            self.h = None
+            if rc != 0 and check:
+                raise PSRFITSError("%s: writing failed (code %d)" % (self.path, rc))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(check=exc_type is None)
+
+    def __del__(self):
+        try:
+            self.close(check=False)
         except Exception:
             pass
 

@@ -81,6 +81,43 @@ def synth_portraits_host(model, phase, sigma, seed, sub0=0):
     return rot
 
 
+def fake_subints_host(model, phase, amp, sigma, seed, sub0=0, npol=1):
+    """Host twin of ppf_fake_subints: data[s][p][n] = amp[s][n] irfft(rfft(model[n])
+    e^{2 pi i k phase[s][n]}) + sigma[n] N(0,1), the noise of polarisation p
+    being noise_block's for channel word n + nchan p."""
+    model = np.asarray(model, dtype=np.float64)
+    nchan, nbin = model.shape
+    phase = np.asarray(phase, dtype=np.float64).reshape(-1, nchan)
+    nsub = phase.shape[0]
+    amp = np.broadcast_to(np.asarray(amp, dtype=np.float64), (nsub, nchan))
+    sigma = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (nchan,))
+    rot = synth_portraits_host(model, phase, 0.0, seed) * amp[..., None]
+    out = np.repeat(rot[:, None], npol, axis=1)
+    if sigma.any():
+        z = noise_block(nsub, nchan * npol, nbin, 1.0, seed, sub0)
+        out = out + z.reshape(nsub, npol, nchan, nbin) * sigma[None, None, :, None]
+    return out
+
+
+def quantize_host(data):
+    """Host twin of ppf_pack_subints (include/ppfit.h): int16 samples and the
+    float32-exact scl / offs (returned as float64) of every row of data
+    [..., nbin].  offs = float32(mid-range), scl = the smallest float32 >=
+    max(hi - offs, offs - lo) / 32767, raw = rint((x - offs) / scl); a
+    constant row takes scl = 1."""
+    x = np.asarray(data, dtype=np.float64)
+    if not np.isfinite(x).all():
+        raise ValueError("quantize_host: non-finite sample")
+    lo, hi = x.min(axis=-1), x.max(axis=-1)
+    offs = (0.5 * (lo + hi)).astype(np.float32).astype(np.float64)
+    w = np.maximum(hi - offs, offs - lo) / 32767.0
+    f = w.astype(np.float32)
+    f = np.where(f.astype(np.float64) < w, np.nextafter(f, np.float32(np.inf)), f)
+    scl = np.where(lo == hi, 1.0, f.astype(np.float64))
+    raw = np.rint((x - offs[..., None]) / scl[..., None]).astype(np.int16)
+    return raw, scl, offs
+
+
 def injected_params(nsub, seed, sub0=0):
     """phi ~ U(-0.1, 0.1), dDM ~ N(3e-4, 2e-4) per subint (examples/example.py:29-31).
 
