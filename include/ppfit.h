@@ -38,6 +38,12 @@
  *                              ppf_gauss_eval is its objective)
  *   ppf_pca_project         <- pplib.reconstruct_portrait and the projection
  *                              pplib.py:1536-1553, ppspline.py:119-129
+ *   ppf_wavelet_smooth_rows <- pplib.wavelet_smooth            pplib.py:1621-1666
+ *   ppf_wavelet_objective_rows <- pplib.fit_wavelet_smooth_function
+ *                              pplib.py:1737-1761
+ *   ppf_smart_smooth_rows   <- pplib.smart_smooth              pplib.py:1668-1735
+ *                              (the db8 stationary transform from its
+ *                              definition; PyWavelets in the reference)
  *   ppf_synth_portraits     <- (test/bench input producer; pplib.make_fake_pulsar
  *                              math, pplib.py:3342-3377, on device)
  *   ppf_fake_subints        <- pplib.make_fake_pulsar's data  pplib.py:3342-3379
@@ -120,7 +126,8 @@ extern "C" {
 #define PPF_K_PCA 15
 #define PPF_K_GAUSS 16
 #define PPF_K_PACK 17
-#define PPF_NUM_KERNELS 18
+#define PPF_K_SWT 18
+#define PPF_NUM_KERNELS 19
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -356,6 +363,49 @@ int ppf_pca_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
 int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
                     const double* mean_prof, int32_t ncomp, const double* eigvec, double* proj,
                     double* reconst);
+
+/* Wavelet smoothing of profiles (pplib.wavelet_smooth, pplib.py:1621-1666):
+ * the undecimated db8 transform with periodic extension to nlevel[r] levels,
+ * the threshold lambda = fact[r] median(|a_L u d_L|) / 0.6745 sqrt(2 ln nbin)
+ * applied to a_L and every d_j (PPF_THRESH_HARD: c -> 0 where |c| < lambda;
+ * PPF_THRESH_SOFT: c -> sign(c) max(|c| - lambda, 0)), and the linear inverse
+ * (DESIGN.md section 9 has the definition; it is built from that definition
+ * and is not pinned against PyWavelets).  nbin even in [16, 8192]
+ * (PPF_ERR_UNSUPPORTED otherwise); every nlevel[r] in 1 .. 13 with nbin a
+ * multiple of 2^nlevel (PPF_ERR_INVALID otherwise; the levels are read on
+ * the host, one stream synchronisation).  The coefficients are workspace
+ * (ppf_set_workspace_limit splits the call over rows).  Results are bitwise
+ * reproducible and a row's do not depend on the other rows of the call.    */
+#define PPF_THRESH_HARD 0
+#define PPF_THRESH_SOFT 1
+int ppf_wavelet_smooth_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin,
+                            const double* rows /* [nrow][nbin] */,
+                            const int32_t* nlevel /* [nrow] */, const double* fact /* [nrow] */,
+                            int32_t threshtype, double* out /* [nrow][nbin] */);
+
+/* pplib.fit_wavelet_smooth_function (pplib.py:1737-1761) of each row at its
+ * (nlevel, fact): obj[r] = -sum_{k>=1} |rfft(s)_k|^2 / (get_noise_PS(s)
+ * sqrt(nbin / 2)) for the smoothed row s -- 0 when the signal is 0, -inf
+ * when the noise is 0, 0 when |red_chi2 - 1| > rchi2_tol -- and red_chi2[r] =
+ * sum ((row - s) / get_noise_PS(row))^2 / nbin (get_red_chi2).             */
+int ppf_wavelet_objective_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* rows,
+                               const int32_t* nlevel, const double* fact, int32_t threshtype,
+                               double rchi2_tol, double* obj /* [nrow] */,
+                               double* red_chi2 /* [nrow] */);
+
+/* pplib.smart_smooth (pplib.py:1668-1735) of each row: for every level 1 ..
+ * try_nlevels, scipy.optimize.brute of the objective above over fact on
+ * linspace(0, 3, 30) (the first minimum) and its fmin finish from that point;
+ * then the first level of least objective, the row smoothed there, and zeros
+ * instead when its red_chi2 is further than rchi2_tol from 1 (zeroed[r] = 1).
+ * An all-zero row stays zero (nlevel 0).  nbin a multiple of 2^try_nlevels,
+ * 1 <= try_nlevels <= 13.  table, when not NULL, receives the polished
+ * objective of every (row, level), [nrow][try_nlevels].                    */
+int ppf_smart_smooth_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* rows,
+                          int32_t try_nlevels, double rchi2_tol, int32_t threshtype,
+                          double* out /* [nrow][nbin] */, int32_t* nlevel /* [nrow] */,
+                          double* fact /* [nrow] */, double* red_chi2 /* [nrow] */,
+                          int32_t* zeroed /* [nrow] */, double* table);
 
 /* out[r] = irfft(rfft(in[r]) * exp(2 pi i k phase[r]))  (rotate_data)     */
 int ppf_rotate_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,

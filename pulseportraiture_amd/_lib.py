@@ -20,7 +20,8 @@ METHODS = {"trust-ncg": PPF_METHOD_TRUST_NCG, "TNC": PPF_METHOD_TNC,
 KERNEL_IDS = {"model_fft": 0, "data_xspec": 1, "solve": 2, "phase_shift": 3,
               "rotate": 4, "rot_accum": 5, "synth": 6, "irfft": 7, "noise": 8,
               "guess": 9, "post": 10, "fit_taylor": 11, "moments": 12, "resid": 13, "unpack": 14,
-              "pca": 15, "gauss": 16, "pack": 17}
+              "pca": 15, "gauss": 16, "pack": 17, "swt": 18}
+PPF_THRESH = {"hard": 0, "soft": 1}
 PPF_SOLVE_EXACT = 1
 PPF_SOLVE_EVAL = 2
 PPF_GUESS_DIRECT = 4
@@ -133,6 +134,13 @@ EXPORTS = {
                            ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_pca_project": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                          ctypes.c_int32, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_wavelet_smooth_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
+                                 ctypes.c_int32, _dp], ctypes.c_int),
+    "ppf_wavelet_objective_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
+                                    ctypes.c_int32, ctypes.c_double, _dp, _dp], ctypes.c_int),
+    "ppf_smart_smooth_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp,
+                               ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _dp, _dp, _dp,
+                               _dp, _dp, _dp], ctypes.c_int),
     "ppf_gauss_eval": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                         ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_gauss_fit_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -1776,6 +1776,230 @@ int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, co
 
 namespace {
 
+// SWT_SWITCH: LG = log2(nbin / 2) of the FFT kernels' lengths, 0 for any
+// other nbin (the generic-length sums)
+#define SWT_SWITCH(L, ...)                                 \
+  switch (L) {                                             \
+    case 5: { constexpr int LG = 5; __VA_ARGS__; } break;    \
+    case 6: { constexpr int LG = 6; __VA_ARGS__; } break;    \
+    case 7: { constexpr int LG = 7; __VA_ARGS__; } break;    \
+    case 8: { constexpr int LG = 8; __VA_ARGS__; } break;    \
+    case 9: { constexpr int LG = 9; __VA_ARGS__; } break;    \
+    case 10: { constexpr int LG = 10; __VA_ARGS__; } break;  \
+    case 11: { constexpr int LG = 11; __VA_ARGS__; } break;  \
+    case 12: { constexpr int LG = 12; __VA_ARGS__; } break;  \
+    default: { constexpr int LG = 0; __VA_ARGS__; } break;   \
+  }
+
+// One pass of the wavelet entry points over rows [r0, r0 + nr): the forward
+// transform, the medians and the rows' noise into the workspace, then `work`.
+struct SwtPlan {
+  int64_t chunk;
+  size_t oMed, oNz, oNoise, oGrid, oPf, oPv, total;
+  SwtPlan(int nbin, int L, int64_t nrow, int64_t ws_limit) {
+    const size_t perW = (size_t)L * 2 * nbin * sizeof(double);
+    const size_t per_row = perW + (size_t)L * (3 + kSwtGrid) * sizeof(double) + 16;
+    chunk = std::max<int64_t>(
+        1, std::min<int64_t>({nrow, ws_limit / (int64_t)(per_row + 64), 65535}));
+    oMed = align256((size_t)chunk * perW);
+    oNz = align256(oMed + (size_t)chunk * L * sizeof(double));
+    oNoise = align256(oNz + (size_t)chunk * sizeof(int));
+    oGrid = align256(oNoise + (size_t)chunk * sizeof(double));
+    oPf = align256(oGrid + (size_t)chunk * L * kSwtGrid * sizeof(double));
+    oPv = align256(oPf + (size_t)chunk * L * sizeof(double));
+    total = oPv + (size_t)chunk * L * sizeof(double);
+  }
+  void bind(SwtArgs& a, void* ws) const {
+    char* base = static_cast<char*>(ws);
+    a.W = reinterpret_cast<double*>(base);
+    a.med = reinterpret_cast<double*>(base + oMed);
+    a.nz = reinterpret_cast<int*>(base + oNz);
+    a.noise = reinterpret_cast<double*>(base + oNoise);
+    a.fgrid = reinterpret_cast<double*>(base + oGrid);
+    a.pfact = reinterpret_cast<double*>(base + oPf);
+    a.pfun = reinterpret_cast<double*>(base + oPv);
+  }
+};
+
+// nbin even in [16, 8192]; every level in 1 .. 13 with nbin divisible by
+// 2^level (pywt.swt's condition)
+int swt_check(ppf_ctx* ctx, int nbin, int threshtype, int* logN) {
+  if (int r = check_nbin_any(ctx, nbin, logN)) return r;
+  if (nbin & 1)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: the transform needs an even nbin", nbin);
+  if (threshtype != PPF_THRESH_HARD && threshtype != PPF_THRESH_SOFT)
+    return fail(ctx, PPF_ERR_INVALID, "threshtype=%d: PPF_THRESH_HARD or PPF_THRESH_SOFT",
+                threshtype);
+  return PPF_OK;
+}
+int swt_check_level(ppf_ctx* ctx, int nbin, int level) {
+  if (level < 1 || level > 13 || nbin % (1 << level))
+    return fail(ctx, PPF_ERR_INVALID, "nlevel=%d: 1..13 with nbin=%d a multiple of 2^nlevel", level,
+                nbin);
+  return PPF_OK;
+}
+
+// the per-row levels on the host, checked; *L their maximum
+int swt_row_levels(ppf_ctx* ctx, int nrow, int nbin, const int32_t* nlevel, int* L) {
+  std::vector<int32_t> h((size_t)nrow);
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), nlevel, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *L = 0;
+  for (int r = 0; r < nrow; ++r) {
+    if (int e = swt_check_level(ctx, nbin, h[r])) return e;
+    *L = std::max(*L, (int)h[r]);
+  }
+  return PPF_OK;
+}
+
+void swt_base_args(SwtArgs& a, int nbin, int L, int threshtype, double tol, const double2* tw) {
+  std::memset(&a, 0, sizeof(a));
+  a.nbin = nbin;
+  a.L = L;
+  a.soft = threshtype == PPF_THRESH_SOFT;
+  a.kc = noise_kc(nbin);
+  a.tol = tol;
+  a.sq2ln = std::sqrt(2.0 * std::log((double)nbin));
+  a.tw = tw;
+}
+
+// forward transform, medians (deepest: only each row's deepest level) and,
+// with noise, get_noise_PS of the nr rows a.rows
+void swt_launch_forward(ppf_ctx* ctx, const SwtArgs& a, int nr, int logN, int deepest, bool noise) {
+  const size_t lds = 2 * (size_t)a.nbin * sizeof(double);
+  hipLaunchKernelGGL(k_swt_forward, dim3(nr), dim3(kBlock), lds, ctx->stream, a);
+  hipLaunchKernelGGL(k_swt_median, dim3(a.L, nr), dim3(kBlock), 0, ctx->stream, a, deepest);
+  if (!noise) return;
+  double* out = const_cast<double*>(a.noise);
+  if (logN < 0)
+    hipLaunchKernelGGL(k_noise_rows_gen, dim3(nr), dim3(kBlock), gen_row_lds(a.nbin), ctx->stream,
+                       a.rows, out, a.kc, a.tw, a.nbin);
+  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_rows<LG>, dim3(nr), dim3(kBlock), 0, ctx->stream,
+                                       a.rows, out, a.kc, a.tw));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppf_wavelet_smooth_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* rows,
+                            const int32_t* nlevel, const double* fact, int32_t threshtype,
+                            double* out) {
+  if (!ctx || !rows || !nlevel || !fact || !out) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nrow <= 0) return PPF_OK;
+  int logN, L;
+  if (int r = swt_check(ctx, nbin, threshtype, &logN)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int r = swt_row_levels(ctx, nrow, nbin, nlevel, &L)) return r;
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  const SwtPlan plan(nbin, L, nrow, ctx->ws_limit);
+  if (int r = ensure(ctx, ctx->buf[kWs], plan.total)) return r;
+  const size_t lds = 2 * (size_t)nbin * sizeof(double);
+  for (int64_t r0 = 0; r0 < nrow; r0 += plan.chunk) {
+    const int nr = (int)std::min<int64_t>(plan.chunk, nrow - r0);
+    SwtArgs a;
+    swt_base_args(a, nbin, L, threshtype, 0.0, tw);
+    plan.bind(a, ctx->buf[kWs].p);
+    a.rows = rows + (size_t)r0 * nbin;
+    a.nlev = nlevel + r0;
+    a.fact = fact + r0;
+    a.out = out + (size_t)r0 * nbin;
+    if (int r = timed(ctx, PPF_K_SWT, [&] {
+          swt_launch_forward(ctx, a, nr, logN, 1, false);
+          hipLaunchKernelGGL(k_swt_smooth, dim3(nr), dim3(kBlock), lds, ctx->stream, a, 0);
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
+int ppf_wavelet_objective_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* rows,
+                               const int32_t* nlevel, const double* fact, int32_t threshtype,
+                               double rchi2_tol, double* obj, double* red_chi2) {
+  if (!ctx || !rows || !nlevel || !fact || !obj || !red_chi2)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nrow <= 0) return PPF_OK;
+  int logN, L;
+  if (int r = swt_check(ctx, nbin, threshtype, &logN)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int r = swt_row_levels(ctx, nrow, nbin, nlevel, &L)) return r;
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  const SwtPlan plan(nbin, L, nrow, ctx->ws_limit);
+  if (int r = ensure(ctx, ctx->buf[kWs], plan.total)) return r;
+  const size_t lds = 2 * (size_t)nbin * sizeof(double);
+  for (int64_t r0 = 0; r0 < nrow; r0 += plan.chunk) {
+    const int nr = (int)std::min<int64_t>(plan.chunk, nrow - r0);
+    SwtArgs a;
+    swt_base_args(a, nbin, L, threshtype, rchi2_tol, tw);
+    plan.bind(a, ctx->buf[kWs].p);
+    a.rows = rows + (size_t)r0 * nbin;
+    a.nlev = nlevel + r0;
+    a.fact = fact + r0;
+    a.o_obj = obj + r0;
+    a.o_rchi2 = red_chi2 + r0;
+    if (int r = timed(ctx, PPF_K_SWT, [&] {
+          swt_launch_forward(ctx, a, nr, logN, 1, true);
+          SWT_SWITCH(logN, hipLaunchKernelGGL(k_swt_objective<LG>, dim3(1, 1, nr), dim3(kBlock),
+                                              lds, ctx->stream, a, 1));
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
+int ppf_smart_smooth_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* rows,
+                          int32_t try_nlevels, double rchi2_tol, int32_t threshtype, double* out,
+                          int32_t* nlevel, double* fact, double* red_chi2, int32_t* zeroed,
+                          double* table) {
+  if (!ctx || !rows || !out || !nlevel || !fact || !red_chi2 || !zeroed)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nrow <= 0) return PPF_OK;
+  int logN;
+  if (int r = swt_check(ctx, nbin, threshtype, &logN)) return r;
+  if (int r = swt_check_level(ctx, nbin, try_nlevels)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int L = try_nlevels;
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  const SwtPlan plan(nbin, L, nrow, ctx->ws_limit);
+  if (int r = ensure(ctx, ctx->buf[kWs], plan.total)) return r;
+  const size_t lds = 2 * (size_t)nbin * sizeof(double);
+  for (int64_t r0 = 0; r0 < nrow; r0 += plan.chunk) {
+    const int nr = (int)std::min<int64_t>(plan.chunk, nrow - r0);
+    SwtArgs a;
+    swt_base_args(a, nbin, L, threshtype, rchi2_tol, tw);
+    plan.bind(a, ctx->buf[kWs].p);
+    a.rows = rows + (size_t)r0 * nbin;
+    a.out = out + (size_t)r0 * nbin;
+    a.o_nlevel = nlevel + r0;
+    a.o_fact = fact + r0;
+    a.o_rchi2 = red_chi2 + r0;
+    a.o_zeroed = zeroed + r0;
+    // (an all-zero row is skipped by the search: its table entries stay 0)
+    HIPCHK(ctx, hipMemsetAsync(a.pfun, 0, (size_t)nr * L * sizeof(double), ctx->stream));
+    if (int r = timed(ctx, PPF_K_SWT, [&] {
+          swt_launch_forward(ctx, a, nr, logN, 0, true);
+          SWT_SWITCH(logN, hipLaunchKernelGGL(k_swt_objective<LG>, dim3(kSwtGrid, L, nr),
+                                              dim3(kBlock), lds, ctx->stream, a, 0));
+          SWT_SWITCH(logN, hipLaunchKernelGGL(k_swt_polish<LG>, dim3(L, nr), dim3(kBlock), lds,
+                                              ctx->stream, a));
+          hipLaunchKernelGGL(k_swt_smooth, dim3(nr), dim3(kBlock), lds, ctx->stream, a, 1);
+        }))
+      return r;
+    if (table)
+      HIPCHK(ctx, hipMemcpyAsync(table + (size_t)r0 * L, a.pfun, (size_t)nr * L * sizeof(double),
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return PPF_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Shapes of a Gaussian-component fit and the slices of its workspace, for
 // `chunk` portraits (ppfit_gauss.hip).
 struct GaussPlan {

@@ -663,6 +663,69 @@ class Engine:
         return (proj.reshape(lead + (nchan, nc)),
                 rec.reshape(lead + (nchan, nbin)) if reconstruct else None)
 
+    def _swt_rows(self, rows, nlevel, fact):
+        dev = self.device
+        r = _dev_f64(rows, dev)
+        r2 = r.reshape(-1, r.shape[-1])
+        nrow = int(r2.shape[0])
+        lev = fa = None
+        if nlevel is not None:
+            lev = _dev_i32(np.array(np.broadcast_to(np.asarray(nlevel, dtype=np.int32).ravel(),
+                                                    (nrow,))), dev)
+            fa = _dev_f64(np.array(np.broadcast_to(np.asarray(fact, dtype=np.float64).ravel(),
+                                                   (nrow,))), dev)
+        return r, r2, nrow, lev, fa
+
+    def wavelet_smooth_rows(self, rows, nlevel, fact, threshtype="hard"):
+        """pplib.wavelet_smooth (pplib.py:1621-1666) of rows [..., nbin] at
+        per-row (or scalar) nlevel and fact (ppf_wavelet_smooth_rows): the
+        smoothed rows, a device tensor."""
+        r, r2, nrow, lev, fa = self._swt_rows(rows, nlevel, fact)
+        out = torch.empty_like(r2)
+        self._chk(self.lib.ppf_wavelet_smooth_rows(
+            self.ctx, nrow, int(r2.shape[1]), _ptr(r2), _ptr(lev), _ptr(fa),
+            _lib.PPF_THRESH[threshtype], _ptr(out)))
+        out._keep = (r2, lev, fa)
+        return out.reshape(r.shape)
+
+    def wavelet_objective_rows(self, rows, nlevel, fact, threshtype="hard", rchi2_tol=0.1):
+        """pplib.fit_wavelet_smooth_function (pplib.py:1737-1761) of rows
+        [..., nbin] at per-row (nlevel, fact) (ppf_wavelet_objective_rows):
+        (objective, red_chi2), device tensors [...]."""
+        r, r2, nrow, lev, fa = self._swt_rows(rows, nlevel, fact)
+        obj = torch.empty(nrow, dtype=torch.float64, device=self.device)
+        rc = torch.empty(nrow, dtype=torch.float64, device=self.device)
+        self._chk(self.lib.ppf_wavelet_objective_rows(
+            self.ctx, nrow, int(r2.shape[1]), _ptr(r2), _ptr(lev), _ptr(fa),
+            _lib.PPF_THRESH[threshtype], float(rchi2_tol), _ptr(obj), _ptr(rc)))
+        obj._keep = (r2, lev, fa)
+        return obj.reshape(r.shape[:-1]), rc.reshape(r.shape[:-1])
+
+    def smart_smooth_rows(self, rows, try_nlevels, rchi2_tol=0.1, threshtype="hard",
+                          table=False):
+        """pplib.smart_smooth (pplib.py:1668-1735) of rows [..., nbin] over
+        levels 1 .. try_nlevels (ppf_smart_smooth_rows).  Returns device
+        tensors: the smoothed rows, the chosen nlevel, fact and red_chi2 and
+        the zeroed flag per row, and with table the polished objective of
+        every (row, level), [..., try_nlevels] (else None)."""
+        dev = self.device
+        r, r2, nrow, _, _ = self._swt_rows(rows, None, None)
+        L = int(try_nlevels)
+        out = torch.empty_like(r2)
+        lev = torch.zeros(nrow, dtype=torch.int32, device=dev)
+        fa = torch.zeros(nrow, dtype=torch.float64, device=dev)
+        rc = torch.zeros(nrow, dtype=torch.float64, device=dev)
+        zeroed = torch.zeros(nrow, dtype=torch.int32, device=dev)
+        tab = torch.zeros((nrow, max(L, 0)), dtype=torch.float64, device=dev) if table else None
+        self._chk(self.lib.ppf_smart_smooth_rows(
+            self.ctx, nrow, int(r2.shape[1]), _ptr(r2), L, float(rchi2_tol),
+            _lib.PPF_THRESH[threshtype], _ptr(out), _ptr(lev), _ptr(fa), _ptr(rc), _ptr(zeroed),
+            _ptr(tab)))
+        out._keep = r2
+        lead = tuple(r.shape[:-1])
+        return (out.reshape(r.shape), lev.reshape(lead), fa.reshape(lead), rc.reshape(lead),
+                zeroed.reshape(lead), tab.reshape(lead + (L,)) if table else None)
+
     def _gauss_inputs(self, data, freqs, errs, params, model_codes, nu_refs):
         dev = self.device
         x = _dev_f64(data, dev)

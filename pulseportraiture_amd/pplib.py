@@ -664,27 +664,142 @@ _NO_SMOOTH = ("wavelet smoothing is unpinned: PyWavelets is not available to pin
               "(only try_nlevels=0, the identity, is implemented)")
 
 
+def _check_wavelet(wavelet):
+    if wavelet != "db8":
+        raise NotImplementedError("wavelet %r: only 'db8' is built" % (wavelet,))
+
+
+def wavelet_smooth(port, wavelet="db8", nlevel=5, threshtype="hard", fact=1.0):
+    """The wavelet-denoised portrait [nchan, nbin] or profile [nbin],
+    pplib.py:1621-1666, on the device (ppf_wavelet_smooth_rows): the
+    undecimated db8 transform with periodic extension to nlevel levels, the
+    threshold fact median(|a_L u d_L|) / 0.6745 sqrt(2 ln nbin) on every
+    coefficient array ('hard' or 'soft'), and the inverse.  Built from the
+    transform's definition and not pinned against PyWavelets (DESIGN.md
+    section 9).  nbin must be a multiple of 2^nlevel (ValueError, as
+    pywt.swt)."""
+    _check_wavelet(wavelet)
+    if threshtype not in ("hard", "soft"):
+        raise ValueError("threshtype %r: 'hard' or 'soft'" % (threshtype,))
+    port = np.asarray(port, dtype=np.float64)
+    nbin, nlevel = port.shape[-1], int(nlevel)
+    if nlevel < 1 or nbin % (1 << nlevel):
+        raise ValueError("nlevel=%d: the length of the data, %d, must be a multiple of 2^nlevel"
+                         % (nlevel, nbin))
+    return _engine().wavelet_smooth_rows(port, nlevel, float(fact), threshtype).cpu().numpy()
+
+
+def get_red_chi2(data, model, errs=None, dof=None):
+    """Reduced chi-squared of 1- or 2-D data against model, pplib.py:727-750:
+    errs default to get_noise of the data (per row), dof to sum(data.shape)."""
+    data, model = np.asarray(data, dtype=np.float64), np.asarray(model, dtype=np.float64)
+    resids = data - model
+    if errs is None:
+        errs = get_noise(data, chans=data.ndim == 2)
+    if dof is None:
+        dof = sum(data.shape)
+    if data.ndim == 1:
+        return np.sum((resids / errs) ** 2.0) / dof
+    return np.array([(resids[ii] / np.asarray(errs)[ii]) ** 2.0
+                     for ii in range(len(resids))]).sum() / dof
+
+
+def fit_wavelet_smooth_function(fact, prof, wavelet, nlevel, threshtype, rchi2_tol):
+    """The negative pseudo-S/N of the profile smoothed at (nlevel, fact) that
+    smart_smooth minimises, pplib.py:1737-1761 (ppf_wavelet_objective_rows):
+    0 when the smoothed profile's reduced chi-squared is further than
+    rchi2_tol from 1."""
+    _check_wavelet(wavelet)
+    obj, _ = _engine().wavelet_objective_rows(np.asarray(prof, dtype=np.float64), int(nlevel),
+                                              float(np.ravel(fact)[0]), threshtype, rchi2_tol)
+    return float(obj.cpu().numpy())
+
+
+def smart_smooth_levels(nbin, try_nlevels=None):
+    """The number of levels smart_smooth searches for profiles of nbin bins
+    (pplib.py:1688-1701): 0 (the input is returned) for try_nlevels=0 or an
+    odd nbin, 1 for an nbin that is no power of two, else try_nlevels or its
+    default log2(nbin)."""
+    if try_nlevels == 0 or nbin % 2 != 0:
+        return 0
+    if nbin & (nbin - 1):
+        return 1
+    return int(np.log2(nbin)) if try_nlevels is None else int(try_nlevels)
+
+
+def smart_smooth(port, try_nlevels=None, rchi2_tol=0.1, full=False, **kwargs):
+    """wavelet_smooth at the (nlevel, fact) of largest pseudo-S/N per profile,
+    pplib.py:1668-1735, every profile of port [nchan, nbin] (or one [nbin])
+    in one device call (ppf_smart_smooth_rows): per level 1 .. try_nlevels the
+    reference's opt.brute over fact (30 grid points on [0, 3], then fmin), the
+    first level of least objective, and zeros when the result's reduced
+    chi-squared is further than rchi2_tol from 1.  kwargs: threshtype is
+    used, nlevel and fact are dropped, wavelet must be 'db8'.  full=True
+    (not in the reference) returns a dict with the search's results too:
+    smooth, nlevel, fact, red_chi2, zeroed and fun_vals [..., try_nlevels]."""
+    _check_wavelet(kwargs.get("wavelet", "db8"))
+    threshtype = kwargs.get("threshtype", "hard")
+    if threshtype not in ("hard", "soft"):
+        raise ValueError("threshtype %r: 'hard' or 'soft'" % (threshtype,))
+    port_in = port
+    port = np.asarray(port, dtype=np.float64)
+    L = smart_smooth_levels(port.shape[-1], try_nlevels)
+    if L == 0:
+        if not full:
+            return port_in
+        lead = port.shape[:-1]
+        return dict(smooth=port, nlevel=np.zeros(lead, dtype=int), fact=np.zeros(lead),
+                    red_chi2=np.zeros(lead), zeroed=np.zeros(lead, dtype=bool), fun_vals=None)
+    out = _engine().smart_smooth_rows(port, L, rchi2_tol, threshtype, table=full)
+    smooth = out[0].cpu().numpy()
+    if not full:
+        return smooth
+    return dict(smooth=smooth, nlevel=out[1].cpu().numpy().astype(int), fact=out[2].cpu().numpy(),
+                red_chi2=out[3].cpu().numpy(), zeroed=out[4].cpu().numpy().astype(bool),
+                fun_vals=out[5].cpu().numpy())
+
+
 def find_significant_eigvec(eigvec, check_max=10, return_max=10, snr_cutoff=150.0,
                             check_crossings=True, check_acorr=True, return_smooth=False,
-                            noise=None, **kwargs):
+                            noise=None, smooth=False, smooth_eigvec=None, **kwargs):
     """Indices of the "significant" eigenvectors (columns of eigvec
     [nbin, ncomp]), pplib.py:1555-1619, with the reference's control flow --
-    its borderline `elif`, which can never add a vector, included.  The
-    smoothing is the identity (the reference's try_nlevels=0 path of
-    smart_smooth); return_smooth=True or another try_nlevels raises
-    NotImplementedError.  Other smart_smooth keywords (rchi2_tol, ...) are
-    accepted and unused.  noise: the vectors' get_noise values if already
-    known (default: get_noise of the examined vectors, on the device)."""
-    if return_smooth or kwargs.get("try_nlevels", 0) not in (0, None):
+    its borderline `elif`, which can never add a vector, included.
+
+    smooth=False (the default): the smoothing is the identity (the
+    reference's try_nlevels=0 path of smart_smooth); return_smooth=True or
+    another try_nlevels raises NotImplementedError, and other smart_smooth
+    keywords (rchi2_tol, ...) are accepted and unused.
+
+    smooth="swt": every vector that may be examined goes through smart_smooth
+    (**kwargs: try_nlevels, rchi2_tol, threshtype) in one device call up
+    front, and the S/N test takes the smoothed vector with the noise of the
+    unsmoothed one, as in the reference; return_smooth=True then returns
+    (ieig, smooth_eigvec [nbin, ncomp], zero but for the columns ieig).
+    smooth_eigvec: those smoothed vectors [nbin, >= ncheck] if already known.
+
+    noise: the vectors' get_noise values if already known (default:
+    get_noise of the examined vectors, on the device)."""
+    if smooth not in (False, None, "swt"):
+        raise NotImplementedError(_NO_SMOOTH)
+    swt = smooth == "swt"
+    if not swt and (return_smooth or kwargs.get("try_nlevels", 0) not in (0, None)):
         raise NotImplementedError(_NO_SMOOTH)
     eigvec = np.asarray(eigvec, dtype=np.float64)
     ncheck = min(max(check_max, return_max), eigvec.shape[1])
     if noise is None and ncheck:
         noise = get_noise(np.ascontiguousarray(eigvec.T[:ncheck]), chans=True)
+    evs = eigvec.T
+    if swt and ncheck:
+        if smooth_eigvec is None:
+            evs = smart_smooth(np.ascontiguousarray(eigvec.T[:ncheck]), **kwargs)
+        else:
+            evs = np.asarray(smooth_eigvec, dtype=np.float64).T
+    smooth_out = np.zeros(eigvec.shape)
     ieig = []
     for ivec in range(ncheck):  # (the reference always has nbin columns)
         add_eigvec = False
-        ev = eigvec.T[ivec]
+        ev = evs[ivec]
         ev_noise = noise[ivec] * np.sqrt(len(ev) / 2.0)
         ev_snr = np.sum(np.abs(np.fft.rfft(ev)[1:]) ** 2) / ev_noise
         if ev_snr >= snr_cutoff:
@@ -704,10 +819,13 @@ def find_significant_eigvec(eigvec, check_max=10, return_max=10, snr_cutoff=150.
                 add_eigvec = True
         if add_eigvec:
             ieig.append(ivec)
+            smooth_out[:, ivec] = ev
         if ivec + 1 == check_max:
             break
         if len(ieig) == return_max:
             break
+    if return_smooth:
+        return np.array(ieig, dtype=int), smooth_out
     return np.array(ieig, dtype=int)
 
 

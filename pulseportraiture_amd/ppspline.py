@@ -8,10 +8,17 @@ space of a few eigenprofiles (ppspline.py:1-20).  The PCA runs on the device
 fit is one scipy.interpolate.splprep call per model on nchan x <= 10 numbers
 (FITPACK, third-party to the reference too).
 
-Not here: wavelet smoothing (smooth=True; PyWavelets is not available to pin
-it against), metafile / joinfile portraits, plotting and the command line.
-Without smoothing the reference's S/N test lets noise eigenvectors through at
-large nbin, so callers should set max_ncomp.
+Wavelet smoothing of the eigenvectors and the mean profile, the reference's
+default, is opt-in as smooth="swt": the undecimated db8 transform built from
+its definition on the device (pplib.smart_smooth, ppf_smart_smooth_rows;
+DESIGN.md section 9), every vector and mean profile of a make_spline_models
+call in one device call.  smooth=True stays refused: it would promise
+PyWavelets' output, which is not available to pin against.  Without smoothing
+(the default here) the reference's S/N test lets noise eigenvectors through at
+large nbin, so callers should pass smooth="swt" or set max_ncomp
+(INTEGRATION.md).
+
+Not here: metafile / joinfile portraits, plotting and the command line.
 """
 import pickle
 
@@ -19,7 +26,8 @@ import numpy as np
 
 from . import archive as _arch
 from . import pplib
-from .pplib import get_noise, gen_spline_portrait, find_significant_eigvec
+from .pplib import (get_noise, gen_spline_portrait, find_significant_eigvec, smart_smooth,
+                    wavelet_smooth)
 
 _NO_SMOOTH = ("smooth=True: " + pplib._NO_SMOOTH)
 
@@ -134,6 +142,24 @@ class DataPortrait(object):
             self.flux_profx = self.portx.mean(axis=1)
             self.norm_values = np.ones(len(self.port))
 
+    def smooth_portrait(self, smart=False, **kwargs):
+        """Wavelet-smooth the portrait and its unzapped channels
+        (pplib.py:400-424): wavelet_smooth(**kwargs), or with smart
+        smart_smooth over min(8, log2 nbin) levels; the noise levels and flux
+        profiles are refreshed."""
+        if smart:
+            def smooth(port):
+                return smart_smooth(port, try_nlevels=min(8, int(np.log2(self.nbin))), **kwargs)
+        else:
+            def smooth(port):
+                return wavelet_smooth(port, **kwargs)
+        self.port = smooth(self.port)
+        self.noise_stds[0, 0] = get_noise(self.port, chans=True)
+        self.flux_prof = self.port.mean(axis=1)
+        self.portx = smooth(self.portx)
+        self.noise_stdsxs = get_noise(self.portx, chans=True)
+        self.flux_profx = self.portx.mean(axis=1)
+
     def pca_weights(self):
         """The PCA (and spline) weights of the unzapped channels (ppspline.py:69)."""
         return self.SNRsxs / np.sum(self.SNRsxs)
@@ -143,34 +169,55 @@ class DataPortrait(object):
         """Make a model based on PCA and B-spline interpolation
         (ppspline.py:34-204; the arguments are the reference's).
 
-        smooth defaults to False, unlike the reference: smooth=True (wavelet
-        smoothing of the eigenvectors and mean profile) raises
-        NotImplementedError.  **kwargs go to find_significant_eigvec."""
+        smooth defaults to False, unlike the reference.  smooth="swt" smooths
+        the eigenvectors and the mean profile with pplib.smart_smooth (the
+        project's from-definition db8 transform) as the reference's
+        smooth=True does with PyWavelets: the significance test, the
+        projections, the model and write_model use the smoothed arrays, kept
+        as self.smooth_eigvec and self.smooth_mean_prof.  smooth=True raises
+        NotImplementedError.  **kwargs go to find_significant_eigvec (and,
+        under smooth="swt", on to smart_smooth for the eigenvectors)."""
         make_spline_models([self], max_ncomp=max_ncomp, smooth=smooth, snr_cutoff=snr_cutoff,
                            rchi2_tol=rchi2_tol, k=k, sfac=sfac, max_nbreak=max_nbreak,
                            model_names=[model_name], quiet=quiet, **kwargs)
 
     def _finish_model(self, mean_prof, eigval, eigvec, max_ncomp, snr_cutoff, rchi2_tol, k, sfac,
-                      max_nbreak, model_name, quiet, kwargs):
+                      max_nbreak, model_name, quiet, kwargs, smoothed=None):
         """make_spline_model after the PCA (ppspline.py:83-204); eigvec
-        [nbin, r] column vectors."""
+        [nbin, r] column vectors.  smoothed (smooth="swt"): the smart_smooth
+        of the leading eigenvectors, as rows, and of the mean profile."""
         port = self.portx
         pca_weights = self.pca_weights()
         freqs = self.freqsxs[0]
         return_max = 10 if max_ncomp is None else min(max_ncomp, 10)
-        ieig = find_significant_eigvec(eigvec, check_max=10, return_max=return_max,
-                                       snr_cutoff=snr_cutoff, return_smooth=False,
-                                       rchi2_tol=rchi2_tol, **kwargs)
+        for attr in ("smooth_eigvec", "smooth_mean_prof"):  # of an earlier model
+            if hasattr(self, attr):
+                delattr(self, attr)
+        if smoothed is None:
+            ieig = find_significant_eigvec(eigvec, check_max=10, return_max=return_max,
+                                           snr_cutoff=snr_cutoff, return_smooth=False,
+                                           rchi2_tol=rchi2_tol, **kwargs)
+            model_vec, model_mean = eigvec, mean_prof
+        else:
+            smooth_cols = np.zeros(eigvec.shape)
+            smooth_cols[:, :len(smoothed[0])] = smoothed[0].T
+            ieig, model_vec = find_significant_eigvec(
+                eigvec, check_max=10, return_max=return_max, snr_cutoff=snr_cutoff,
+                return_smooth=True, rchi2_tol=rchi2_tol, smooth="swt", smooth_eigvec=smooth_cols,
+                **kwargs)
+            model_mean = smoothed[1]
         ncomp = len(ieig)
         nfull = len(self.freqs[0])
         if ncomp == 0:  # a model with the constant average portrait
             proj_port = port[:, :0]
-            modelx = reconst_port = np.tile(mean_prof, (len(freqs), 1))
-            model = np.tile(mean_prof, (nfull, 1))
+            modelx = reconst_port = np.tile(model_mean, (len(freqs), 1))
+            model = np.tile(model_mean, (nfull, 1))
             (tck, u) = [np.array([]), np.array([]), 0], np.array([])
             fp, ier, msg = None, None, None
         else:
-            basis = np.ascontiguousarray(eigvec[:, ieig])
+            # (the projections are about the unsmoothed mean profile, as in
+            # the reference)
+            basis = np.ascontiguousarray(model_vec[:, ieig])
             proj, rec = pplib._engine().pca_project(port, mean_prof,
                                                     np.ascontiguousarray(basis.T),
                                                     reconstruct=True)
@@ -181,11 +228,13 @@ class DataPortrait(object):
             if ier > 1:
                 print("Something went wrong in si.splprep for %s:\n%s" % (self.source, msg))
             # both portraits in one device call
-            both = gen_spline_portrait(mean_prof, np.concatenate([freqs, self.freqs[0]]), basis,
+            both = gen_spline_portrait(model_mean, np.concatenate([freqs, self.freqs[0]]), basis,
                                        tck)
             modelx, model = both[:len(freqs)], both[len(freqs):]
         self.ieig, self.ncomp = ieig, ncomp
         self.eigvec, self.eigval, self.mean_prof = eigvec, eigval, mean_prof
+        if smoothed is not None:
+            self.smooth_mean_prof, self.smooth_eigvec = model_mean, model_vec
         self.proj_port, self.reconst_port = proj_port, reconst_port
         self.tck, self.u, self.fp, self.ier, self.msg = tck, u, fp, ier, msg
         self.model_name = self.datafile + ".spl" if model_name is None else model_name
@@ -203,10 +252,16 @@ class DataPortrait(object):
 
     def write_model(self, outfile, quiet=False):
         """Write the model as the reference's pickle (ppspline.py:206-230):
-        [model_name, source, datafile, mean_prof, eigvec[:, ieig], tck], in
-        protocol 2 so that the Python-2 reference reads it too."""
-        basis = self.eigvec[:, self.ieig] if len(self.ieig) else self.eigvec[:, []]
-        blob = pickle.dumps([self.model_name, self.source, self.datafile, self.mean_prof,
+        [model_name, source, datafile, mean_prof, eigvec[:, ieig], tck] -- the
+        smoothed mean profile and eigenvectors when the model was made with
+        smooth="swt" -- in protocol 2 so that the Python-2 reference reads it
+        too."""
+        if hasattr(self, "smooth_eigvec"):
+            eigvec, mean_prof = self.smooth_eigvec, self.smooth_mean_prof
+        else:
+            eigvec, mean_prof = self.eigvec, self.mean_prof
+        basis = eigvec[:, self.ieig] if len(self.ieig) else eigvec[:, []]
+        blob = pickle.dumps([self.model_name, self.source, self.datafile, mean_prof,
                              np.ascontiguousarray(basis), self.tck], protocol=2)
         # numpy 2 names its array constructor numpy._core.multiarray, which a
         # Python-2 numpy does not have; numpy.core.multiarray resolves in
@@ -223,9 +278,10 @@ def make_spline_models(portraits, max_ncomp=10, smooth=False, snr_cutoff=150.0, 
                        k=3, sfac=1.0, max_nbreak=None, model_names=None, quiet=False, **kwargs):
     """make_spline_model for a list of DataPortraits whose condensed
     portraits share one shape (pulsars x receivers): one batched PCA call,
-    then the host steps per portrait.  The results are those of the
-    one-by-one calls, exactly."""
-    if smooth:
+    then (smooth="swt") one smart_smooth call for every portrait's leading
+    eigenvectors and mean profile, then the host steps per portrait.  The
+    results are those of the one-by-one calls, exactly."""
+    if smooth and smooth != "swt":
         raise NotImplementedError(_NO_SMOOTH)
     portraits = list(portraits)
     if not portraits:
@@ -245,10 +301,34 @@ def make_spline_models(portraits, max_ncomp=10, smooth=False, snr_cutoff=150.0, 
         np.stack([dp.pca_weights() for dp in portraits]))
     mean, eigval, info = mean.cpu().numpy(), eigval.cpu().numpy(), info.cpu().numpy()
     eigvec = eigvec.cpu().numpy()
+    nbin = shape[1]
+    if smooth and nbin % 2 != 0:
+        print("nbin = %d is odd; cannot wavelet_smooth.\n" % nbin)
+        smooth = False
+    elif smooth and nbin & (nbin - 1):
+        print("nbin = %d is not a power of two; can only try wavelet_smooth to one level; "
+              "recommend resampling to a power-of-two number of phase bins.\n" % nbin)
+    smoothed = [None] * len(portraits)
+    if smooth:
+        # the keywords find_significant_eigvec hands on to smart_smooth; the
+        # mean profiles get rchi2_tol alone (ppspline.py:101-102)
+        sm_kw = {key: val for key, val in kwargs.items()
+                 if key not in ("check_crossings", "check_acorr", "noise", "smooth_eigvec")}
+        ncheck = min(10, eigvec.shape[1])
+        vecs = eigvec[:, :ncheck].reshape(-1, nbin)
+        if any(key in sm_kw for key in ("try_nlevels", "threshtype")):
+            svecs = smart_smooth(vecs, rchi2_tol=rchi2_tol, **sm_kw)
+            smean = smart_smooth(mean, rchi2_tol=rchi2_tol)
+        else:  # the same search for both: one device call
+            both = smart_smooth(np.concatenate([vecs, mean]), rchi2_tol=rchi2_tol, **sm_kw)
+            svecs, smean = both[:len(vecs)], both[len(vecs):]
+        svecs = svecs.reshape(len(portraits), ncheck, nbin)
+        smoothed = [(svecs[i], smean[i]) for i in range(len(portraits))]
     for i, dp in enumerate(portraits):
         if not info[i, 1]:
             print("PCA of %s did not converge in %d sweeps." % (dp.datafile, info[i, 0]))
         dp.pca_info = info[i]
         dp._finish_model(mean[i], eigval[i], np.ascontiguousarray(eigvec[i].T), max_ncomp,
-                         snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_names[i], quiet, kwargs)
+                         snr_cutoff, rchi2_tol, k, sfac, max_nbreak, model_names[i], quiet, kwargs,
+                         smoothed[i])
     return portraits
