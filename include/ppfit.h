@@ -36,6 +36,9 @@
  *   ppf_gauss_fit_batch     <- pplib.fit_gaussian_portrait     pplib.py:1924-2052
  *                              (lmfit's leastsq, batched over portraits;
  *                              ppf_gauss_eval is its objective)
+ *   ppf_gauss_bank          <- ppgauss.GaussianSelector (ppgauss.py:374-640,
+ *                              a person at a plot): the matched-filter bank
+ *                              of pplib.auto_gaussian_profiles
  *   ppf_pca_project         <- pplib.reconstruct_portrait and the projection
  *                              pplib.py:1536-1553, ppspline.py:119-129
  *   ppf_wavelet_smooth_rows <- pplib.wavelet_smooth            pplib.py:1621-1666
@@ -127,7 +130,8 @@ extern "C" {
 #define PPF_K_GAUSS 16
 #define PPF_K_PACK 17
 #define PPF_K_SWT 18
-#define PPF_NUM_KERNELS 19
+#define PPF_K_GBANK 19
+#define PPF_NUM_KERNELS 20
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -496,6 +500,31 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
                         const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
                         double* params, double* param_errs, double* cov, double* chi2,
                         int32_t* info);
+
+/* ppf_gauss_bank: the matched-filter bank of the automatic component search
+ * (pplib.auto_gaussian_profiles).  For profile p, width w and bin j the
+ * template g is the unit-amplitude component as the fit builds it --
+ * gen_gaussian_profile([0, 0, loc_j, widths[w], 1.0], nbin) with loc_j the
+ * centre of bin j, the same bin-centre wrap, |z| < 20 support and rescale
+ * factor -- scattered by 1 / (1 + 2 pi i k taun[p]) when taun[p] != 0.  With
+ * c = <resid[p], g> and gg = <g, g>: amp = c / gg and s2 = c^2 / (gg
+ * errs[p]^2) where c > 0, else 0.  best[p] is the maximum of s2 over (w, j),
+ * ties to the smaller width index, then the smaller bin; with no s2 > 0
+ * best[p] is zeros and best_idx[p] is -1, -1.  c is computed as a circular
+ * correlation on the spectra, gg by Parseval.
+ *   Limits: nbin a power of two in [64, 8192], 1 <= nwid <= 64
+ * (PPF_ERR_UNSUPPORTED otherwise); widths outside (0, 0.25] are
+ * PPF_ERR_INVALID.  Scratch is workspace (ppf_set_workspace_limit splits the
+ * call over profiles).  Results are bitwise reproducible and do not depend on
+ * how many profiles share the call.                                        */
+int ppf_gauss_bank(ppf_ctx* ctx, int32_t nprof, int32_t nbin, int32_t nwid,
+                   const double* resid /* DEVICE [nprof][nbin] */,
+                   const double* errs /* DEVICE [nprof], > 0 */,
+                   const double* taun /* DEVICE [nprof], tau / nbin; 0 = unscattered */,
+                   const double* widths /* HOST [nwid], FWHM in (0, 0.25] */,
+                   double* s2 /* DEVICE [nprof][nwid][nbin], may be NULL */,
+                   double* best /* DEVICE [nprof][4]: s2, loc, wid, amp */,
+                   int32_t* best_idx /* DEVICE [nprof][2]: width index, bin; -1, -1 if none */);
 
 /* B-spline (PCA) template rows (gen_spline_portrait, pplib.py:932-956, as
  * read_spline_model builds them, pplib.py:2961-2993): row r at freqs[r] is

@@ -20,7 +20,7 @@ METHODS = {"trust-ncg": PPF_METHOD_TRUST_NCG, "TNC": PPF_METHOD_TNC,
 KERNEL_IDS = {"model_fft": 0, "data_xspec": 1, "solve": 2, "phase_shift": 3,
               "rotate": 4, "rot_accum": 5, "synth": 6, "irfft": 7, "noise": 8,
               "guess": 9, "post": 10, "fit_taylor": 11, "moments": 12, "resid": 13, "unpack": 14,
-              "pca": 15, "gauss": 16, "pack": 17, "swt": 18}
+              "pca": 15, "gauss": 16, "pack": 17, "swt": 18, "gbank": 19}
 PPF_THRESH = {"hard": 0, "soft": 1}
 PPF_SOLVE_EXACT = 1
 PPF_SOLVE_EVAL = 2
@@ -147,6 +147,8 @@ EXPORTS = {
                              ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
                              ctypes.c_double, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp],
                             ctypes.c_int),
+    "ppf_gauss_bank": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
+                        _dp, ctypes.c_void_p, _dp, _dp, _dp], ctypes.c_int),
     "ppf_synth_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, ctypes.c_double,
                              ctypes.c_uint64, ctypes.c_int64, _dp], ctypes.c_int),

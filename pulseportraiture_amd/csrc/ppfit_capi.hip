@@ -2189,4 +2189,58 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
   return PPF_OK;
 }
 
+int ppf_gauss_bank(ppf_ctx* ctx, int32_t nprof, int32_t nbin, int32_t nwid, const double* resid,
+                   const double* errs, const double* taun, const double* widths, double* s2,
+                   double* best, int32_t* best_idx) {
+  if (!ctx || !resid || !errs || !taun || !widths || !best || !best_idx)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nprof <= 0) return PPF_OK;
+  const int l = ilog2_exact(nbin);
+  if (l < 6 || nbin > 8192)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: a power of two in [64, 8192]", nbin);
+  if (nwid < 1 || nwid > kBankMaxWid)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nwid=%d: 1..%d widths in a bank", nwid, kBankMaxWid);
+  GaussBankArgs a;
+  for (int w = 0; w < nwid; ++w) {
+    if (!(widths[w] > 0.0) || !(widths[w] <= 0.25))
+      return fail(ctx, PPF_ERR_INVALID, "widths[%d]=%g: a FWHM in (0, 0.25]", w, widths[w]);
+    a.widths[w] = widths[w];
+  }
+  for (int w = nwid; w < kBankMaxWid; ++w) a.widths[w] = 0.0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int logN = l - 1, NH = nbin / 2 + 1;
+  if (int r = twiddles(ctx, nbin, &a.tw)) return r;
+  // scratch per profile: the residual spectrum and one record per width
+  const size_t bSpec = (size_t)NH * sizeof(double2), bPart = (size_t)nwid * 4 * sizeof(double);
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)nprof, ctx->ws_limit / (int64_t)(bSpec + bPart + 512), 65535}));
+  const size_t oPart = align256((size_t)chunk * bSpec);
+  if (int r = ensure(ctx, ctx->buf[kWs], oPart + (size_t)chunk * bPart)) return r;
+  char* base = static_cast<char*>(ctx->buf[kWs].p);
+  double2* rspec = reinterpret_cast<double2*>(base);
+  a.nbin = nbin;
+  a.nwid = nwid;
+  a.fwhm = 2.0 * std::sqrt(2.0 * std::log(2.0));
+  a.sqrt2pi = std::sqrt(2.0 * M_PI);
+  a.rspec = rspec;
+  a.part = reinterpret_cast<double*>(base + oPart);
+  for (int64_t p0 = 0; p0 < nprof; p0 += chunk) {
+    const int np = (int)std::min<int64_t>(chunk, nprof - p0);
+    a.errs = errs + p0;
+    a.taun = taun + p0;
+    a.s2 = s2 ? s2 + (size_t)p0 * nwid * nbin : nullptr;
+    a.best = best + (size_t)p0 * 4;
+    a.best_idx = best_idx + (size_t)p0 * 2;
+    if (int r = timed(ctx, PPF_K_GBANK, [&] {
+          launch_rfft_rows(ctx->stream, logN, nbin, np, resid + (size_t)p0 * nbin, rspec, a.tw);
+          LOGN_SWITCH(logN, hipLaunchKernelGGL(k_gauss_bank<LG>, dim3(nwid, np), dim3(kBlock), 0,
+                                               ctx->stream, a));
+          hipLaunchKernelGGL(k_gauss_bank_best, dim3((np + 63) / 64), dim3(64), 0, ctx->stream, a,
+                             np);
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
 }  // extern "C"

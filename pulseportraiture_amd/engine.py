@@ -795,6 +795,32 @@ class Engine:
         out["params"]._keep = (x, f, e, par, fl, code, nu)
         return out
 
+    def gauss_bank(self, resid, errs, taun, widths, full=False):
+        """The matched-filter bank of the automatic component search
+        (ppf_gauss_bank): for resid [nprof, nbin], errs and taun (tau / nbin)
+        [nprof] and the host list widths [nwid] of FWHMs, best [nprof, 4] =
+        s2, loc, wid, amp of the most significant unit-amplitude component
+        and best_idx [nprof, 2] = its width index and bin (-1, -1 and zeros
+        when no correlation is positive); full=True adds the s2 map [nprof,
+        nwid, nbin].  Device tensors out."""
+        dev = self.device
+        r = _dev_f64(resid, dev)
+        r = r.reshape(-1, r.shape[-1]).contiguous()
+        nprof, nbin = (int(v) for v in r.shape)
+        e = _dev_f64(np.broadcast_to(np.asarray(errs, dtype=np.float64), (nprof,)).copy(), dev)
+        t = _dev_f64(np.broadcast_to(np.asarray(taun, dtype=np.float64), (nprof,)).copy(), dev)
+        wh = np.ascontiguousarray(widths, dtype=np.float64).reshape(-1)
+        nwid = len(wh)
+        s2 = torch.empty((nprof, nwid, nbin), dtype=torch.float64, device=dev) if full else None
+        best = torch.zeros((nprof, 4), dtype=torch.float64, device=dev)
+        idx = torch.full((nprof, 2), -1, dtype=torch.int32, device=dev)
+        self._chk(self.lib.ppf_gauss_bank(
+            self.ctx, nprof, nbin, nwid, _ptr(r), _ptr(e), _ptr(t),
+            wh.ctypes.data_as(ctypes.c_void_p), _ptr(s2) if full else None, _ptr(best),
+            _ptr(idx)))
+        best._keep = (r, e, t)
+        return (best, idx, s2) if full else (best, idx)
+
     def _irf_call(self, nrow, nbin, rows, f, fh, DM, P, wids, irf_types, chan_bw, out):
         code = {"rect": 0, "gauss": 1}
         types = []

@@ -7,8 +7,11 @@ reads.  The fits -- lmfit's leastsq in the reference, one core and no
 Jacobian -- run as one batched Levenberg-Marquardt call with an analytic
 Jacobian (ppf_gauss_fit_batch, ppfit_gauss.hip).
 
-Not here: the interactive GaussianSelector (give auto_gauss or init_params),
-metafile / joinfile portraits, residplot and the command line.
+The interactive GaussianSelector is replaced by an automatic search
+(max_ngauss > 0: pplib.auto_gaussian_profiles, a matched-filter pursuit on
+the device); auto_gauss and init_params remain.
+
+Not here: metafile / joinfile portraits, residplot and the command line.
 """
 import time
 
@@ -18,10 +21,11 @@ from . import pplib
 from . import ppspline
 from .pplib import (default_model, scattering_alpha, gaussian_profile, get_noise,
                     fit_phase_shift, fit_portrait, fit_gaussian_profile, fit_gaussian_portraits,
-                    guess_fit_freq, read_model, rotate_data)
+                    guess_fit_freq, read_model, rotate_data, auto_gaussian_profiles)
 
-_NO_SELECTOR = ("the interactive GaussianSelector is not supported: give auto_gauss (one "
-                "component, fitted automatically) or init_params")
+_NO_SELECTOR = ("the interactive GaussianSelector is not supported: give max_ngauss (the "
+                "automatic component search), auto_gauss (one component, fitted "
+                "automatically) or init_params")
 
 
 class DataPortrait(ppspline.DataPortrait):
@@ -39,16 +43,22 @@ class DataPortrait(ppspline.DataPortrait):
 
     # -- the initial profile fit ------------------------------------------
     def fit_profile(self, profile, tau=0.0, fixscat=True, auto_gauss=0.0, profile_fit_flags=None,
-                    show=False, init_params=None):
+                    show=False, init_params=None, max_ngauss=0):
         """Fit Gaussian components to a profile (ppgauss.py:27-53) without
         the GUI: auto_gauss != 0 is the initial width [rot] of one component
         placed by fit_phase_shift (ppgauss.py:419, 442-459); init_params (DC,
-        tau [bin], then loc, wid, amp per component) seeds several."""
+        tau [bin], then loc, wid, amp per component) seeds several; with
+        neither, max_ngauss > 0 searches for up to that many components
+        (pplib.auto_gaussian_profiles)."""
         profile = np.asarray(profile, dtype=np.float64)
         fit_scattering = not fixscat
-        if init_params is None:
-            if not auto_gauss:
+        if init_params is None and not auto_gauss:
+            if not max_ngauss:
                 raise NotImplementedError(_NO_SELECTOR)
+            self._take_search(auto_gaussian_profiles(
+                [profile], None, max_ngauss, self._search_tau(tau, fixscat), fit_scattering)[0])
+            return
+        if init_params is None:
             if fit_scattering and tau == 0.0:
                 tau = 0.1  # (ppgauss.py:415-416)
             errs = get_noise(profile)
@@ -69,10 +79,37 @@ class DataPortrait(ppspline.DataPortrait):
         self.init_param_errs = fgp.fit_errs
         self.ngauss = (len(self.init_params) - 2) // 3
 
+    @staticmethod
+    def _search_tau(tau, fixscat):
+        return 0.1 if (not fixscat and tau == 0.0) else tau  # (ppgauss.py:415-416)
+
+    def _take_search(self, found):
+        """The automatic search's result as the profile fit."""
+        if not found.ngauss:
+            raise RuntimeError("%s: the automatic component search found no significant "
+                               "component in the reference profile" % self.datafile)
+        self.profile_fit = found
+        self.init_params = found.fitted_params
+        self.init_param_errs = found.fit_errs
+        self.ngauss = found.ngauss
+
+    def _ref_profile(self, ref_prof):
+        """The profile of the channels around nu_ref (ppgauss.py:120-141)."""
+        self.nu_ref, self.bw_ref = ref_prof
+        if self.nu_ref is None:
+            self.nu_ref = self.nu0
+        if self.bw_ref is None:
+            self.bw_ref = abs(self.bw)
+        f = self.freqs[0]
+        ok = np.flatnonzero((self.nu_ref - self.bw_ref / 2 < f) *
+                            (self.nu_ref + self.bw_ref / 2 > f) *
+                            self.masks[0, 0].mean(axis=1))
+        return np.take(self.port, ok, axis=0).mean(axis=0)  # unweighted
+
     # -- the model ----------------------------------------------------------
     def _start_model(self, modelfile, ref_prof, tau, fixloc, fixwid, fixamp, fixscat, fixalpha,
                      scattering_index, model_code, fiducial_gaussian, auto_gauss, model_name,
-                     init_params):
+                     init_params, max_ngauss=0):
         """The starting parameters and flags (ppgauss.py:99-159)."""
         if modelfile:
             (self.model_name, self.model_code, self.nu_ref, self.ngauss, self.init_model_params,
@@ -89,18 +126,10 @@ class DataPortrait(ppspline.DataPortrait):
         self.fitalpha = int(not self.fixalpha)
         self.model_name = self.source if model_name is None else model_name
         if init_params is not None or not len(self.init_params):
-            self.nu_ref, self.bw_ref = ref_prof
-            if self.nu_ref is None:
-                self.nu_ref = self.nu0
-            if self.bw_ref is None:
-                self.bw_ref = abs(self.bw)
-            f = self.freqs[0]
-            ok = np.flatnonzero((self.nu_ref - self.bw_ref / 2 < f) *
-                                (self.nu_ref + self.bw_ref / 2 > f) *
-                                self.masks[0, 0].mean(axis=1))
-            profile = np.take(self.port, ok, axis=0).mean(axis=0)  # unweighted
+            profile = self._ref_profile(ref_prof)
             self.fit_profile(profile, tau=tau, fixscat=fixscat, auto_gauss=auto_gauss,
-                             profile_fit_flags=None, show=False, init_params=init_params)
+                             profile_fit_flags=None, show=False, init_params=init_params,
+                             max_ngauss=max_ngauss)
         ip = np.asarray(self.init_params, dtype=np.float64)
         comps = np.zeros((self.ngauss, 6))  # slopes and spectral indices start at 0
         comps[:, 0], comps[:, 2], comps[:, 4] = ip[2::3], ip[3::3], ip[4::3]
@@ -119,17 +148,19 @@ class DataPortrait(ppspline.DataPortrait):
                             scattering_index=scattering_alpha, model_code=default_model, niter=0,
                             fiducial_gaussian=False, auto_gauss=0.0, writemodel=False,
                             outfile=None, writeerrfile=False, errfile=None, model_name=None,
-                            residplot=None, quiet=False, init_params=None):
+                            residplot=None, quiet=False, init_params=None, max_ngauss=0):
         """Fit a Gaussian-component model with independently evolving
-        components (ppgauss.py:55-238; the arguments are the reference's,
-        init_params seeds the profile fit in place of the GUI)."""
+        components (ppgauss.py:55-238; the arguments are the reference's;
+        in place of the GUI, init_params seeds the profile fit or
+        max_ngauss > 0 searches for its components)."""
         make_gaussian_models(
             [self], modelfiles=[modelfile], ref_prof=ref_prof, tau=tau, fixloc=fixloc,
             fixwid=fixwid, fixamp=fixamp, fixscat=fixscat, fixalpha=fixalpha,
             scattering_index=scattering_index, model_code=model_code, niter=niter,
             fiducial_gaussian=fiducial_gaussian, auto_gauss=auto_gauss, writemodel=writemodel,
             outfiles=[outfile], writeerrfile=writeerrfile, errfiles=[errfile],
-            model_names=[model_name], residplot=residplot, quiet=quiet, init_params=[init_params])
+            model_names=[model_name], residplot=residplot, quiet=quiet, init_params=[init_params],
+            max_ngauss=max_ngauss)
 
     def _fit_inputs(self):
         """fit_gaussian_portrait's arguments of model_iteration (ppgauss.py:246-250)."""
@@ -229,12 +260,15 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
                          scattering_index=scattering_alpha, model_code=default_model, niter=0,
                          fiducial_gaussian=False, auto_gauss=0.0, writemodel=False, outfiles=None,
                          writeerrfile=False, errfiles=None, model_names=None, residplot=None,
-                         quiet=False, init_params=None):
+                         quiet=False, init_params=None, max_ngauss=0):
     """make_gaussian_model for a list of DataPortraits whose unzapped
     portraits share one shape and component count: each iteration's portrait
-    fits run in one ppf_gauss_fit_batch call.  The results are those of the
-    one-by-one calls, exactly.  modelfiles, outfiles, errfiles, model_names
-    and init_params are lists (None: the default for every portrait)."""
+    fits run in one ppf_gauss_fit_batch call, and with max_ngauss > 0 the
+    reference profiles of all portraits that need the component search go
+    through one pplib.auto_gaussian_profiles call.  The results are those of
+    the one-by-one calls, exactly.  modelfiles, outfiles, errfiles,
+    model_names and init_params are lists (None: the default for every
+    portrait)."""
     if residplot:
         raise NotImplementedError("residplot (plotting) is not supported")
     dps = list(portraits)
@@ -244,6 +278,15 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
     modelfiles, outfiles, errfiles, model_names, init_params = (
         [None] * n if v is None else list(v)
         for v in (modelfiles, outfiles, errfiles, model_names, init_params))
+    search = [i for i, dp in enumerate(dps)
+              if not modelfiles[i] and init_params[i] is None and not len(dp.init_params)
+              and not auto_gauss and max_ngauss]
+    if search:
+        found = auto_gaussian_profiles([dps[i]._ref_profile(ref_prof) for i in search], None,
+                                       max_ngauss, DataPortrait._search_tau(tau, fixscat),
+                                       not fixscat)
+        for i, f in zip(search, found):
+            dps[i]._take_search(f)
     for i, dp in enumerate(dps):
         if modelfiles[i]:
             if outfiles[i] is None:
@@ -252,7 +295,7 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
             errfiles[i] = outfiles[i] + "_errs"
         dp._start_model(modelfiles[i], ref_prof, tau, fixloc, fixwid, fixamp, fixscat, fixalpha,
                         scattering_index, model_code, fiducial_gaussian, auto_gauss,
-                        model_names[i], init_params[i])
+                        model_names[i], init_params[i], max_ngauss)
         dp.nu_fit = guess_fit_freq(dp.freqsxs[0], dp.SNRsxs)
         dp.niter = dp.itern = max(int(niter), 0)
         dp.model_params = np.copy(dp.init_model_params)

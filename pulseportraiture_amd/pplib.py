@@ -331,6 +331,35 @@ def profile_fit_flags(nparam, fit_flags=None, fit_scattering=False):
                                                          for i in range(1, nparam - 1)]
 
 
+def _fit_gaussian_profiles(datas, init_params, errs, fit_flags=None, fit_scattering=False):
+    """fit_gaussian_profile's solver call for profiles of one length and
+    component count, in one device call: (fitted_params, fit_errs, portrait
+    DataBunch) per profile."""
+    datas = [np.asarray(d, dtype=np.float64) for d in datas]
+    nbin = len(datas[0])
+    pars, fls, es = [], [], []
+    for data, init, err in zip(datas, init_params, errs):
+        init = np.asarray(init, dtype=np.float64)
+        nparam = len(init)
+        ngauss = (nparam - 2) // 3
+        flags = profile_fit_flags(nparam, fit_flags, fit_scattering)
+        par, fl = np.zeros(2 + 6 * ngauss), np.zeros(2 + 6 * ngauss, dtype=bool)
+        par[:2], fl[:2] = init[:2], flags[:2]
+        for k in range(3):
+            par[2 + 2 * k::6], fl[2 + 2 * k::6] = init[2 + k::3], flags[2 + k::3]
+        pars.append(par)
+        fls.append(fl)
+        es.append(_row_errs((np.asarray(err, dtype=np.float64) + np.zeros(nbin))[None],
+                            (1, nbin)))
+    n = len(datas)
+    fgps = fit_gaussian_portraits(["111"] * n, [d[None] for d in datas], pars, [0.0] * n, es, fls,
+                                  [False] * n, get_bin_centers(nbin), [np.ones(1)] * n, [1.0] * n,
+                                  quiet=True)
+    keep = np.sort(np.concatenate([[0, 1]] + [np.arange(2 + 2 * k, len(pars[0]), 6)
+                                             for k in range(3)])).astype(int)
+    return [(fgp.fitted_params[keep], fgp.fit_errs[keep], fgp) for fgp in fgps]
+
+
 def fit_gaussian_profile(data, init_params, errs, fit_flags=None, fit_scattering=False,
                          quiet=True):
     """Fit Gaussian components to a profile (pplib.py:1842-1922): the
@@ -338,21 +367,9 @@ def fit_gaussian_profile(data, init_params, errs, fit_flags=None, fit_scattering
     parameters fixed at 0 under the linear code, where the value is the
     parameter exactly.  Returns fitted_params, fit_errs, residuals, chi2, dof."""
     data = np.asarray(data, dtype=np.float64)
-    init_params = np.asarray(init_params, dtype=np.float64)
-    nparam = len(init_params)
-    ngauss = (nparam - 2) // 3
-    flags = profile_fit_flags(nparam, fit_flags, fit_scattering)
-    par, fl = np.zeros(2 + 6 * ngauss), np.zeros(2 + 6 * ngauss, dtype=bool)
-    par[:2], fl[:2] = init_params[:2], flags[:2]
-    for k in range(3):
-        par[2 + 2 * k::6], fl[2 + 2 * k::6] = init_params[2 + k::3], flags[2 + k::3]
-    e = _row_errs((np.asarray(errs, dtype=np.float64) + np.zeros(len(data)))[None],
-                  (1, len(data)))
-    fgp = fit_gaussian_portraits(["111"], [data[None]], [par], [0.0], [e], [fl], [False],
-                                 get_bin_centers(len(data)), [np.ones(1)], [1.0], quiet=True)[0]
-    keep = np.sort(np.concatenate([[0, 1]] + [np.arange(2 + 2 * k, len(par), 6)
-                                             for k in range(3)])).astype(int)
-    fitted, fit_errs = fgp.fitted_params[keep], fgp.fit_errs[keep]
+    ngauss = (len(init_params) - 2) // 3
+    fitted, fit_errs, fgp = _fit_gaussian_profiles([data], [init_params], [errs], fit_flags,
+                                                   fit_scattering)[0]
     residuals = data - gen_gaussian_profile(fitted, len(data))
     if not quiet:
         print("---------------------------------------------------------------")
@@ -367,6 +384,128 @@ def fit_gaussian_profile(data, init_params, errs, fit_flags=None, fit_scattering
         print("---------------------------------------------------------------")
     return DataBunch(fitted_params=fitted, fit_errs=fit_errs, residuals=residuals, chi2=fgp.chi2,
                      dof=fgp.dof, lm_results=fgp.lm_results)
+
+
+# ---------------------------------------------------------------------------
+# The automatic component search: a headless stand-in for ppgauss's
+# interactive GaussianSelector (ppgauss.py:374-640)
+# ---------------------------------------------------------------------------
+AUTO_GAUSS_WID_MAX = 0.25  # the fit's upper bound on a width (pplib.py:1976)
+AUTO_GAUSS_MAX = 16        # PPF_K_GAUSS: components in one fit
+AUTO_GAUSS_EDGE = 1e-6     # a fitted amp or wid this close to a bound is on it
+
+
+def auto_gaussian_widths(nbin, nwid=16, wid_max=AUTO_GAUSS_WID_MAX):
+    """The FWHMs of the filter bank: two bins up to the fit's bound."""
+    return np.geomspace(2.0 / nbin, wid_max, nwid)
+
+
+def auto_gaussian_accept(status, chi2_new, chi2_old, params, nbin, wid_max=AUTO_GAUSS_WID_MAX):
+    """Whether a refit with one more component is kept: it converged, it
+    pays for its three parameters by the BIC, and no amplitude or width sits
+    on a bound (where lmfit's errors mean nothing)."""
+    wids, amps = np.asarray(params[3::3]), np.asarray(params[4::3])
+    return bool(status in (1, 2, 3)
+                and chi2_new + 3.0 * np.log(nbin) < chi2_old
+                and np.all(np.abs(amps) > AUTO_GAUSS_EDGE)
+                and np.all(wids > AUTO_GAUSS_EDGE)
+                and np.all(wids < wid_max - AUTO_GAUSS_EDGE))
+
+
+def auto_gaussian_profiles(profiles, errs=None, max_ngauss=8, tau=0.0, fit_scattering=False,
+                           min_snr=5.0, nwid=16, quiet=True):
+    """Find and fit the Gaussian components of profiles [nprof, nbin] with no
+    starting values: a greedy matched-filter pursuit.  It starts from zero
+    components, DC at the profile's mean (the fitted constant).  Each stage finds the
+    most significant unit-amplitude component in every profile's residual
+    (ppf_gauss_bank, one device call), appends it and refits DC and all
+    components (tau [bin] too when fit_scattering) in one batched
+    Levenberg-Marquardt call.  A profile stops when nothing reaches min_snr,
+    at max_ngauss components, or when the refit is not accepted
+    (auto_gaussian_accept); it then keeps its previous fit.  errs=None takes
+    get_noise of each profile.
+
+    Returns one DataBunch per profile: fitted_params (DC, tau, then loc, wid,
+    amp per component in order of discovery), fit_errs, chi2, dof, ngauss,
+    residuals, lm_results (None with no component) and history -- per stage
+    s2, candidate, chi2_old, chi2_new, accepted and stop."""
+    if max_ngauss > AUTO_GAUSS_MAX:
+        raise ValueError("max_ngauss=%d: at most %d components in a fit"
+                         % (max_ngauss, AUTO_GAUSS_MAX))
+    profs = [np.asarray(p, dtype=np.float64) for p in profiles]
+    nprof = len(profs)
+    if not nprof:
+        return []
+    nbin = len(profs[0])
+    if any(p.ndim != 1 or len(p) != nbin for p in profs):
+        raise ValueError("profiles of one length per call")
+    if errs is None:
+        errs = [get_noise(p) for p in profs]
+    errs = np.broadcast_to(np.asarray(errs, dtype=np.float64), (nprof,)).copy()
+    widths = auto_gaussian_widths(nbin, nwid)
+    eng = _engine()
+    out = []
+    for p, e in zip(profs, errs):
+        dc = np.mean(p)  # the least-squares fit of the zero-component model
+        resid = p - dc
+        out.append(DataBunch(fitted_params=np.array([dc, float(tau)]),
+                             fit_errs=np.array([e / np.sqrt(nbin), 0.0]),
+                             chi2=float(np.sum((resid / e) ** 2)), dof=nbin - 1, ngauss=0,
+                             residuals=resid, lm_results=None, history=[]))
+    active = list(range(nprof))
+    while active:
+        run = []
+        for i in active:
+            b = out[i]
+            if b.ngauss >= max_ngauss:
+                b.history.append(DataBunch(s2=np.nan, candidate=None, chi2_old=b.chi2,
+                                           chi2_new=np.nan, accepted=False, stop="max_ngauss"))
+            else:
+                run.append(i)
+        if not run:
+            break
+        best, _ = eng.gauss_bank(np.stack([out[i].residuals for i in run]), errs[run],
+                                 np.array([out[i].fitted_params[1] / nbin for i in run]), widths)
+        best = best.cpu().numpy()
+        fit = []
+        for i, (s2, loc, wid, amp) in zip(run, best):
+            if s2 < min_snr ** 2:
+                out[i].history.append(DataBunch(s2=float(s2), candidate=None,
+                                                chi2_old=out[i].chi2, chi2_new=np.nan,
+                                                accepted=False, stop="min_snr"))
+            else:
+                fit.append((i, float(s2), np.array([loc, wid, amp])))
+        active = []
+        if not fit:
+            break
+        res = _fit_gaussian_profiles(
+            [profs[i] for i, _, _ in fit],
+            [np.concatenate([out[i].fitted_params, c]) for i, _, c in fit],
+            [errs[i] for i, _, _ in fit], None, fit_scattering)
+        for (i, s2, cand), (fitted, fit_errs, fgp) in zip(fit, res):
+            b = out[i]
+            ok = auto_gaussian_accept(fgp.lm_results.status, fgp.chi2, b.chi2, fitted, nbin)
+            b.history.append(DataBunch(s2=s2, candidate=cand, chi2_old=b.chi2, chi2_new=fgp.chi2,
+                                       accepted=ok, stop=None if ok else "rejected"))
+            if not ok:
+                continue
+            b.fitted_params, b.fit_errs, b.chi2, b.dof = fitted, fit_errs, fgp.chi2, fgp.dof
+            b.lm_results = fgp.lm_results
+            b.ngauss += 1
+            b.residuals = profs[i] - gen_gaussian_profile(fitted, nbin)
+            active.append(i)
+    if not quiet:
+        for i, b in enumerate(out):
+            print("profile %d: %d Gaussians, chi-sq %.6g, DoF %d, stopped by %s"
+                  % (i, b.ngauss, b.chi2, b.dof, b.history[-1].stop))
+    return out
+
+
+def auto_gaussian_profile(profile, errs=None, max_ngauss=8, tau=0.0, fit_scattering=False,
+                          min_snr=5.0, nwid=16, quiet=True):
+    """auto_gaussian_profiles for one profile."""
+    return auto_gaussian_profiles([profile], None if errs is None else [errs], max_ngauss, tau,
+                                  fit_scattering, min_snr, nwid, quiet)[0]
 
 
 # ---------------------------------------------------------------------------
