@@ -36,6 +36,8 @@
  *   ppf_gauss_fit_batch     <- pplib.fit_gaussian_portrait     pplib.py:1924-2052
  *                              (lmfit's leastsq, batched over portraits;
  *                              ppf_gauss_eval is its objective)
+ *   ppf_gauss_fit_join_batch <- the same with join_params (metafile portraits;
+ *                              ppf_gauss_eval_join is its objective)
  *   ppf_gauss_bank          <- ppgauss.GaussianSelector (ppgauss.py:374-640,
  *                              a person at a plot): the matched-filter bank
  *                              of pplib.auto_gaussian_profiles
@@ -500,6 +502,38 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
                         const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
                         double* params, double* param_errs, double* cov, double* chi2,
                         int32_t* info);
+
+/* Joint fits of several receivers' portraits (fit_gaussian_portrait with
+ * join_params, pplib.py:923-929, 1992-2001).  The rows of a portrait belong to
+ * njoin groups (one per receiver; bands may overlap, so groups may interleave)
+ * and the external vector has npar = 3 + 6 ngauss + 2 njoin entries: DC, tau,
+ * the components, then phase_g [rot] and DM_g per group, then alpha (lmfit's
+ * order).  Row n of group g = join_of[n] is the model row rotated as
+ * rotate_data(row, phase_g, DM_g, P, f_n, nu_ref) does it: every harmonic k
+ * of the model times exp(+2 pi i k theta_n), theta_n = phase_g + DM_g
+ * dm_coef[n], the imaginary part at DC and Nyquist dropped after the product.
+ * The caller passes dm_coef[n] = Dconst (f_n^-2 - nu_ref^-2) / P.  The model
+ * is rotated, not the data: at the Nyquist harmonic the two are different
+ * functions.  The join parameters are unbounded.  join_of [nport][nchan]
+ * int32 in 0 .. njoin - 1 (PPF_ERR_INVALID otherwise, checked before the fit
+ * reads it), dm_coef [nport][nchan] double; the other arguments, the results
+ * and the guarantees are those of ppf_gauss_eval and ppf_gauss_fit_batch,
+ * which are unchanged.
+ *   Limits: 1 <= njoin <= 8 and 3 + 6 ngauss + 2 njoin <= 99
+ * (PPF_ERR_UNSUPPORTED otherwise).                                          */
+int ppf_gauss_eval_join(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        int32_t njoin, const double* data, const double* freqs,
+                        const double* errs, const double* params, const int32_t* code,
+                        const double* nu_ref, const int32_t* join_of /* [nport][nchan] */,
+                        const double* dm_coef /* [nport][nchan] */, double* chi2, double* jtr,
+                        double* jtj);
+int ppf_gauss_fit_join_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                             int32_t ngauss, int32_t njoin, const double* data,
+                             const double* freqs, const double* errs, const double* init,
+                             const int32_t* flags, const int32_t* code, const double* nu_ref,
+                             const int32_t* join_of, const double* dm_coef, double ftol,
+                             double xtol, int32_t max_nfev, double* params, double* param_errs,
+                             double* cov, double* chi2, int32_t* info);
 
 /* ppf_gauss_bank: the matched-filter bank of the automatic component search
  * (pplib.auto_gaussian_profiles).  For profile p, width w and bin j the

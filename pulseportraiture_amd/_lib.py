@@ -147,6 +147,13 @@ EXPORTS = {
                              ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
                              ctypes.c_double, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp],
                             ctypes.c_int),
+    "ppf_gauss_eval_join": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                             ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                             _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_gauss_fit_join_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp, _dp,
+                                  _dp, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                  _dp, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_gauss_bank": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                         _dp, ctypes.c_void_p, _dp, _dp, _dp], ctypes.c_int),
     "ppf_synth_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,

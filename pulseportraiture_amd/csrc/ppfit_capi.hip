@@ -2005,22 +2005,32 @@ namespace {
 struct GaussPlan {
   int npar, KT, KB, npairs, NH, logN;
   int64_t chunk;
-  size_t oRows, oSpec, oDspec, oCoef, oTaun, oGram, oPext, oLm, oState, total;
+  size_t oRows, oSpec, oDspec, oCoef, oTaun, oGram, oPext, oLm, oState, oBad, total;
 };
 
-int gauss_plan(ppf_ctx* ctx, int nport, int nchan, int nbin, int ngauss, bool fit, GaussPlan* g) {
+// njoin < 0: no join parameters (one receiver)
+int gauss_plan(ppf_ctx* ctx, int nport, int nchan, int nbin, int ngauss, int njoin, bool fit,
+               GaussPlan* g) {
   if (ngauss < 1 || ngauss > kFitMaxGauss)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "ngauss=%d: 1..%d components in a fit", ngauss,
                 kFitMaxGauss);
+  const bool join = njoin >= 0;
+  if (join && (njoin < 1 || njoin > kFitMaxJoin))
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "njoin=%d: 1..%d join groups in a fit", njoin,
+                kFitMaxJoin);
+  if (join && 3 + 6 * ngauss + 2 * njoin > kGfMaxPar)
+    return fail(ctx, PPF_ERR_UNSUPPORTED,
+                "ngauss=%d, njoin=%d: 3 + 6 ngauss + 2 njoin = %d parameters, at most %d", ngauss,
+                njoin, 3 + 6 * ngauss + 2 * njoin, kGfMaxPar);
   if (nchan < 1 || nchan > kFitMaxChan)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: 1..%d channels in a fit", nchan, kFitMaxChan);
   const int l = ilog2_exact(nbin);
   if (l < 6 || nbin > 8192)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: a power of two in [64, 8192]", nbin);
   g->logN = l - 1;
-  g->npar = 3 + 6 * ngauss;
+  g->npar = 3 + 6 * ngauss + (join ? 2 * njoin : 0);
   g->KT = 1 + 3 * ngauss;
-  g->KB = g->KT + 2;
+  g->KB = g->KT + 2 + (join ? 1 : 0);
   g->npairs = g->KB * (g->KB + 1) / 2;
   g->NH = nbin / 2 + 1;
   const size_t rows = (size_t)nchan;
@@ -2046,14 +2056,20 @@ int gauss_plan(ppf_ctx* ctx, int nport, int nchan, int nbin, int ngauss, bool fi
   g->oLm = align256(g->oPext + c * bPext);
   g->oState = align256(g->oLm + c * bLm);
   g->total = g->oState + c * sizeof(GaussFitState);
+  g->oBad = g->total;
+  if (join) g->total = g->oBad + 256;  // the flag of k_gauss_join_check
   return PPF_OK;
 }
 
-void gauss_args(const GaussPlan& g, char* base, int nchan, int nbin, int ngauss, GaussFitArgs* a) {
+void gauss_args(const GaussPlan& g, char* base, int nchan, int nbin, int ngauss, int njoin,
+                GaussFitArgs* a) {
   a->nchan = nchan;
   a->nbin = nbin;
   a->ngauss = ngauss;
   a->npar = g.npar;
+  a->njoin = njoin > 0 ? njoin : 0;
+  a->join_of = nullptr;
+  a->dm_coef = nullptr;
   a->max_nfev = 0;
   a->fwhm = 2.0 * std::sqrt(2.0 * std::log(2.0));
   a->sqrt2pi = std::sqrt(2.0 * M_PI);
@@ -2078,39 +2094,68 @@ void gauss_args(const GaussPlan& g, char* base, int nchan, int nbin, int ngauss,
 int gauss_evaluate(ppf_ctx* ctx, const GaussPlan& g, const GaussFitArgs& a, int np, int fit,
                    const double2* tw) {
   return timed(ctx, PPF_K_GAUSS, [&] {
-    hipLaunchKernelGGL(k_gauss_basis, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+    if (a.njoin)
+      hipLaunchKernelGGL(k_gauss_basis<true>, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+    else
+      hipLaunchKernelGGL(k_gauss_basis<false>, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
     launch_rfft_rows(ctx->stream, g.logN, a.nbin, np * a.nchan * g.KT, a.rows,
                      const_cast<double2*>(a.spec), tw);
-    hipLaunchKernelGGL(k_gauss_gram, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_gauss_step, dim3(np), dim3(256), 0, ctx->stream, a, fit);
+    if (a.njoin) {
+      hipLaunchKernelGGL(k_gauss_gram<true>, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+      hipLaunchKernelGGL(k_gauss_step<true>, dim3(np), dim3(256), 0, ctx->stream, a, fit);
+    } else {
+      hipLaunchKernelGGL(k_gauss_gram<false>, dim3(a.nchan, np), dim3(256), 0, ctx->stream, a);
+      hipLaunchKernelGGL(k_gauss_step<false>, dim3(np), dim3(256), 0, ctx->stream, a, fit);
+    }
   });
 }
 
-}  // namespace
+// PPF_ERR_INVALID when a join_of entry of the call is outside 0 .. njoin - 1;
+// one small kernel and one read of its flag before any fit kernel reads
+// join_of
+int gauss_join_check(ppf_ctx* ctx, const GaussPlan& g, char* base, int64_t nrow, int njoin,
+                     const int32_t* join_of) {
+  int* bad = reinterpret_cast<int*>(base + g.oBad);
+  int hbad = 0;
+  HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(k_gauss_join_check, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0,
+                     ctx->stream, join_of, nrow, njoin, bad);
+  HIPCHK(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (hbad) return fail(ctx, PPF_ERR_INVALID, "join_of: a group outside 0..%d", njoin - 1);
+  return PPF_OK;
+}
 
-extern "C" {
-
-int ppf_gauss_eval(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
-                   const double* data, const double* freqs, const double* errs,
-                   const double* params, const int32_t* code, const double* nu_ref, double* chi2,
-                   double* jtr, double* jtj) {
-  if (!ctx || !data || !freqs || !errs || !params || !code || !nu_ref || !chi2 || !jtr || !jtj)
+int gauss_eval_impl(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                    int32_t njoin, const double* data, const double* freqs, const double* errs,
+                    const double* params, const int32_t* code, const double* nu_ref,
+                    const int32_t* join_of, const double* dm_coef, double* chi2, double* jtr,
+                    double* jtj) {
+  if (!ctx || !data || !freqs || !errs || !params || !code || !nu_ref || !chi2 || !jtr || !jtj ||
+      (njoin >= 0 && (!join_of || !dm_coef)))
     return fail(ctx, PPF_ERR_INVALID, "null argument");
   if (nport <= 0) return PPF_OK;
   GaussPlan g;
-  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, false, &g)) return r;
+  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, njoin, false, &g)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   if (int r = ensure(ctx, ctx->buf[kWs], g.total)) return r;
+  char* base = static_cast<char*>(ctx->buf[kWs].p);
+  if (njoin >= 0)
+    if (int r = gauss_join_check(ctx, g, base, (int64_t)nport * nchan, njoin, join_of)) return r;
   GaussFitArgs a;
-  gauss_args(g, static_cast<char*>(ctx->buf[kWs].p), nchan, nbin, ngauss, &a);
+  gauss_args(g, base, nchan, nbin, ngauss, njoin, &a);
   for (int64_t p0 = 0; p0 < nport; p0 += g.chunk) {
     const int np = (int)std::min<int64_t>(g.chunk, nport - p0);
     a.freqs = freqs + (size_t)p0 * nchan;
     a.errs = errs + (size_t)p0 * nchan;
     a.code = code + (size_t)p0 * 3;
     a.nu_ref = nu_ref + p0;
+    if (njoin >= 0) {
+      a.join_of = join_of + (size_t)p0 * nchan;
+      a.dm_coef = dm_coef + (size_t)p0 * nchan;
+    }
     a.chi2 = chi2 + p0;
     a.jtr = jtr + (size_t)p0 * g.npar;
     a.jtj = jtj + (size_t)p0 * g.npar * g.npar;
@@ -2127,27 +2172,29 @@ int ppf_gauss_eval(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int
   return PPF_OK;
 }
 
-int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
-                        const double* data, const double* freqs, const double* errs,
-                        const double* init, const int32_t* flags, const int32_t* code,
-                        const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
-                        double* params, double* param_errs, double* cov, double* chi2,
-                        int32_t* info) {
+int gauss_fit_impl(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                   int32_t njoin, const double* data, const double* freqs, const double* errs,
+                   const double* init, const int32_t* flags, const int32_t* code,
+                   const double* nu_ref, const int32_t* join_of, const double* dm_coef,
+                   double ftol, double xtol, int32_t max_nfev, double* params,
+                   double* param_errs, double* cov, double* chi2, int32_t* info) {
   if (!ctx || !data || !freqs || !errs || !init || !flags || !code || !nu_ref || !params ||
-      !param_errs || !chi2 || !info)
+      !param_errs || !chi2 || !info || (njoin >= 0 && (!join_of || !dm_coef)))
     return fail(ctx, PPF_ERR_INVALID, "null argument");
   if (nport <= 0) return PPF_OK;
   if (!(ftol >= 0.0) || !(xtol >= 0.0) || max_nfev < 0)
     return fail(ctx, PPF_ERR_INVALID, "ftol=%g xtol=%g max_nfev=%d", ftol, xtol, max_nfev);
   GaussPlan g;
-  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, true, &g)) return r;
+  if (int r = gauss_plan(ctx, nport, nchan, nbin, ngauss, njoin, true, &g)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   if (int r = ensure(ctx, ctx->buf[kWs], g.total)) return r;
   char* base = static_cast<char*>(ctx->buf[kWs].p);
+  if (njoin >= 0)
+    if (int r = gauss_join_check(ctx, g, base, (int64_t)nport * nchan, njoin, join_of)) return r;
   GaussFitArgs a;
-  gauss_args(g, base, nchan, nbin, ngauss, &a);
+  gauss_args(g, base, nchan, nbin, ngauss, njoin, &a);
   a.ftol = ftol;
   a.xtol = xtol;
   a.max_nfev = max_nfev;
@@ -2161,6 +2208,10 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
     a.code = code + (size_t)p0 * 3;
     a.nu_ref = nu_ref + p0;
     a.flags = flags + (size_t)p0 * g.npar;
+    if (njoin >= 0) {
+      a.join_of = join_of + (size_t)p0 * nchan;
+      a.dm_coef = dm_coef + (size_t)p0 * nchan;
+    }
     a.chi2 = chi2 + p0;
     a.params = params + (size_t)p0 * g.npar;
     a.perrs = param_errs + (size_t)p0 * g.npar;
@@ -2170,8 +2221,12 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
     if (int r = timed(ctx, PPF_K_GAUSS, [&] {
           launch_rfft_rows(ctx->stream, g.logN, nbin, np * nchan,
                            data + (size_t)p0 * nchan * nbin, const_cast<double2*>(a.dspec), tw);
-          hipLaunchKernelGGL(k_gauss_init, dim3(np), dim3(256), 0, ctx->stream, a,
-                             init + (size_t)p0 * g.npar, a.flags);
+          if (a.njoin)
+            hipLaunchKernelGGL(k_gauss_init<true>, dim3(np), dim3(256), 0, ctx->stream, a,
+                               init + (size_t)p0 * g.npar, a.flags);
+          else
+            hipLaunchKernelGGL(k_gauss_init<false>, dim3(np), dim3(256), 0, ctx->stream, a,
+                               init + (size_t)p0 * g.npar, a.flags);
         }))
       return r;
     // the host reads the portraits' states once per iteration and stops when
@@ -2187,6 +2242,54 @@ int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin
     }
   }
   return PPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppf_gauss_eval(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                   const double* data, const double* freqs, const double* errs,
+                   const double* params, const int32_t* code, const double* nu_ref, double* chi2,
+                   double* jtr, double* jtj) {
+  return gauss_eval_impl(ctx, nport, nchan, nbin, ngauss, -1, data, freqs, errs, params, code,
+                         nu_ref, nullptr, nullptr, chi2, jtr, jtj);
+}
+
+int ppf_gauss_eval_join(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        int32_t njoin, const double* data, const double* freqs,
+                        const double* errs, const double* params, const int32_t* code,
+                        const double* nu_ref, const int32_t* join_of, const double* dm_coef,
+                        double* chi2, double* jtr, double* jtj) {
+  if (njoin < 0) return fail(ctx, PPF_ERR_UNSUPPORTED, "njoin=%d: 1..%d join groups in a fit",
+                             njoin, kFitMaxJoin);
+  return gauss_eval_impl(ctx, nport, nchan, nbin, ngauss, njoin, data, freqs, errs, params, code,
+                         nu_ref, join_of, dm_coef, chi2, jtr, jtj);
+}
+
+int ppf_gauss_fit_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const double* data, const double* freqs, const double* errs,
+                        const double* init, const int32_t* flags, const int32_t* code,
+                        const double* nu_ref, double ftol, double xtol, int32_t max_nfev,
+                        double* params, double* param_errs, double* cov, double* chi2,
+                        int32_t* info) {
+  return gauss_fit_impl(ctx, nport, nchan, nbin, ngauss, -1, data, freqs, errs, init, flags, code,
+                        nu_ref, nullptr, nullptr, ftol, xtol, max_nfev, params, param_errs, cov,
+                        chi2, info);
+}
+
+int ppf_gauss_fit_join_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                             int32_t ngauss, int32_t njoin, const double* data,
+                             const double* freqs, const double* errs, const double* init,
+                             const int32_t* flags, const int32_t* code, const double* nu_ref,
+                             const int32_t* join_of, const double* dm_coef, double ftol,
+                             double xtol, int32_t max_nfev, double* params, double* param_errs,
+                             double* cov, double* chi2, int32_t* info) {
+  if (njoin < 0) return fail(ctx, PPF_ERR_UNSUPPORTED, "njoin=%d: 1..%d join groups in a fit",
+                             njoin, kFitMaxJoin);
+  return gauss_fit_impl(ctx, nport, nchan, nbin, ngauss, njoin, data, freqs, errs, init, flags,
+                        code, nu_ref, join_of, dm_coef, ftol, xtol, max_nfev, params, param_errs,
+                        cov, chi2, info);
 }
 
 int ppf_gauss_bank(ppf_ctx* ctx, int32_t nprof, int32_t nbin, int32_t nwid, const double* resid,

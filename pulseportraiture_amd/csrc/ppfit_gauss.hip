@@ -10,15 +10,26 @@
 // differentiated on its support with fact, the wrap and the support held fixed
 // (they are piecewise constant).
 //
+// Joint fits of several receivers (JOIN instantiations; fit_gaussian_portrait
+// with join_params, pplib.py:923-929, 1992-2001): row n of join group g is the
+// model row rotated as rotate_data does it, every model-side spectrum times
+// R_k = exp(2 pi i k theta_n), theta_n = phase_g + DM_g dm_coef[n].  Its
+// derivative to theta_n is one more Gram row, 2 pi i k R_k S_k X_k; phase_g
+// and DM_g reach it through the chain-rule scalars [join_of[n] == g] and
+// [join_of[n] == g] dm_coef[n].  The no-join instantiations do the arithmetic
+// they did before there was a JOIN flag.
+//
 //   k_gauss_basis  per (portrait, channel) row: the unscattered model row and
 //                  three derivative profiles per component (d/dloc_n,
 //                  d/dwid_n, d/damp_n) in the time domain, the chain-rule
-//                  scalars from the evolved to the external parameters, tau_n;
+//                  scalars from the evolved to the external parameters, tau_n
+//                  (JOIN: and the join parameters' scalars);
 //   (k_rfft_rows   the existing row transform, forward only)
 //   k_gauss_gram   per row, on the spectra (Parseval, DC and Nyquist weights
 //                  folded in): the Gram matrix of K = 3 ngauss + 3 rows --
 //                  the residual, the constant, the tau_n derivative and the
-//                  scattered derivative profiles -- so chi^2, J^T r and
+//                  scattered derivative profiles (JOIN: all rotated, and the
+//                  theta_n derivative as row K) -- so chi^2, J^T r and
 //                  J^T J of the row come from one product;
 //   k_gauss_init   external -> internal parameters (lmfit's MINUIT bound
 //                  transforms), free-parameter count, evaluation cap;
@@ -73,11 +84,15 @@ __device__ __forceinline__ double gf_evolve(int code, double lr, double df, doub
   return __dadd_rn(__dmul_rn(df, evo), par);  // linear
 }
 
-// lmfit's bounds (pplib.py:1964-1988): 1 lower only (tau, amp >= 0), 2
-// two-sided (0 <= wid <= wid_max), 0 none
-__device__ __forceinline__ int gf_kind(int q, int npar) {
+// lmfit's bounds (pplib.py:1964-2001): 1 lower only (tau, amp >= 0), 2
+// two-sided (0 <= wid <= wid_max), 0 none (JOIN: the join parameters,
+// 2 + 6 ngauss <= q < npar - 1, among them)
+template <bool JOIN>
+__device__ __forceinline__ int gf_kind(int q, int npar, int ngauss) {
   if (q == 1) return 1;
   if (q < 2 || q == npar - 1) return 0;
+  if constexpr (JOIN)
+    if (q >= 2 + 6 * ngauss) return 0;
   const int m = (q - 2) % 6;
   return m == 2 ? 2 : (m == 4 ? 1 : 0);
 }
@@ -105,10 +120,14 @@ __device__ __forceinline__ double gf_to_int(int kind, double v, double hi) {
 }
 
 // the Gram row of external parameter q: 1 the constant, 2 the tau_n
-// derivative, 3 + 3 c + {0 loc, 1 wid, 2 amp}
-__device__ __forceinline__ int gf_basis(int q, int npar) {
+// derivative, 3 + 3 c + {0 loc, 1 wid, 2 amp}, 3 + 3 ngauss the theta_n
+// derivative (JOIN: phase_g and DM_g of every join group)
+template <bool JOIN>
+__device__ __forceinline__ int gf_basis(int q, int npar, int ngauss) {
   if (q == 0) return 1;
   if (q == 1 || q == npar - 1) return 2;
+  if constexpr (JOIN)
+    if (q >= 2 + 6 * ngauss) return 3 + 3 * ngauss;
   return 3 + 3 * ((q - 2) / 6) + ((q - 2) % 6) / 2;
 }
 __device__ __forceinline__ int gf_tri(int i, int j) {  // packed lower triangle, i >= j
@@ -116,6 +135,7 @@ __device__ __forceinline__ int gf_tri(int i, int j) {  // packed lower triangle,
 }
 
 // grid (nchan, nport)
+template <bool JOIN>
 __global__ __launch_bounds__(256) void k_gauss_basis(GaussFitArgs a) {
   constexpr int NT = 256;
   const int n = blockIdx.x, p = blockIdx.y;
@@ -147,6 +167,13 @@ __global__ __launch_bounds__(256) void k_gauss_basis(GaussFitArgs a) {
     cf[0] = 1.0;
     cf[1] = pw / (double)nbin;
     cf[npar - 1] = tn * log(f / nu_ref);
+  }
+  if constexpr (JOIN) {
+    // d theta_n / d phase_g, d theta_n / d DM_g
+    if (tid < 2 * a.njoin) {
+      const bool mine = a.join_of[row] == (tid >> 1);
+      cf[2 + 6 * a.ngauss + tid] = mine ? ((tid & 1) ? a.dm_coef[row] : 1.0) : 0.0;
+    }
   }
   for (int c = 0; c < a.ngauss; ++c) {
     const double* q6 = par + 2 + 6 * c;
@@ -225,20 +252,31 @@ __global__ __launch_bounds__(256) void k_gauss_basis(GaussFitArgs a) {
 constexpr int kGfTile = 32;                        // harmonics per LDS tile
 constexpr int kGfStride = 2 * kGfTile + 1;         // odd row stride: no bank conflicts
 constexpr int kGfMaxBasis = 3 * kFitMaxGauss + 3;  // 51
-constexpr int kGfPairsPerThread = (kGfMaxBasis * (kGfMaxBasis + 1) / 2 + 255) / 256;  // 6
+// pairs of one thread: 6 without and with the join row (1326 and 1378 pairs)
+constexpr int kGfPairsPerThread = (kGfMaxBasis * (kGfMaxBasis + 1) / 2 + 255) / 256;
+static_assert(((kGfMaxBasis + 1) * (kGfMaxBasis + 2) / 2 + 255) / 256 == kGfPairsPerThread,
+              "the join row needs no further pair per thread");
 
+template <bool JOIN>
 __global__ __launch_bounds__(256) void k_gauss_gram(GaussFitArgs a) {
   const int n = blockIdx.x, p = blockIdx.y;
   if (a.state && a.state[p].done) return;
-  __shared__ double tile[kGfMaxBasis * kGfStride];
+  __shared__ double tile[(kGfMaxBasis + (JOIN ? 1 : 0)) * kGfStride];
   const int tid = threadIdx.x;
-  const int nbin = a.nbin, NH = nbin / 2 + 1, KT = 1 + 3 * a.ngauss, KB = KT + 2;
+  const int nbin = a.nbin, NH = nbin / 2 + 1, KT = 1 + 3 * a.ngauss;
+  const int KB = KT + 2 + (JOIN ? 1 : 0);
   const size_t row = (size_t)p * a.nchan + n;
   const double2* X = a.spec + row * KT * NH;
   const double2* D = a.dspec + row * NH;
   const double tn = a.taun[row];
   const double ierr = 1.0 / a.errs[row];
   const int npairs = KB * (KB + 1) / 2;
+  double theta = 0.0;  // the row's rotation, reduced to (-1/2, 1/2]: k is an integer
+  if constexpr (JOIN) {
+    const double* jp = a.pext + (size_t)p * a.npar + 2 + 6 * a.ngauss + 2 * a.join_of[row];
+    theta = fma(jp[1], a.dm_coef[row], jp[0]);
+    theta -= rint(theta);
+  }
   int pi[kGfPairsPerThread], pj[kGfPairsPerThread];
   double acc[kGfPairsPerThread];
 #pragma unroll
@@ -269,8 +307,29 @@ __global__ __launch_bounds__(256) void k_gauss_gram(GaussFitArgs a) {
           const double2 S2 = cmul(S, S);
           const double c2 = 2.0 * M_PI * (double)k;
           v = cmul(cmk(c2 * S2.y, -c2 * S2.x), X[k]);
-        } else {
+        } else if (!JOIN || b < KT + 2) {
           v = cmul(S, X[(size_t)(b - 2) * NH + k]);
+        }
+        if constexpr (JOIN) {
+          // R = exp(2 pi i k theta_n) on the model side; the theta_n
+          // derivative of R S X_0 is 2 pi i k R S X_0.  The rows are rotated
+          // as time series (gen_gaussian_portrait scatters, transforms back
+          // and hands the rows to rotate_data): at Nyquist the scattered
+          // spectrum has lost its imaginary part before R multiplies it.
+          const bool nyq = 2 * k == nbin;
+          double rs, rc;
+          sincospi(2.0 * (double)k * theta, &rs, &rc);
+          const double2 R = cmk(rc, rs);
+          if (b == 0 || b == KT + 2) {
+            double2 m = cmul(S, X[k]);
+            if (nyq) m.y = 0.0;
+            m = cmul(R, m);
+            const double c2 = 2.0 * M_PI * (double)k;
+            v = b == 0 ? csub(D[k], m) : cmk(-c2 * m.y, c2 * m.x);
+          } else if (b >= 2) {
+            if (nyq) v.y = 0.0;
+            v = cmul(R, v);
+          }
         }
         // Parseval: sum_j x_j y_j = (1 / nbin) sum_k w_k Re(X_k conj(Y_k)),
         // w = 1 at DC and Nyquist, 2 between
@@ -300,6 +359,7 @@ __global__ __launch_bounds__(256) void k_gauss_gram(GaussFitArgs a) {
 }
 
 // grid (nport), npar threads used
+template <bool JOIN>
 __global__ __launch_bounds__(256) void k_gauss_init(GaussFitArgs a, const double* __restrict__ init,
                                                     const int* __restrict__ flags) {
   const int p = blockIdx.x, tid = threadIdx.x, npar = a.npar;
@@ -307,7 +367,7 @@ __global__ __launch_bounds__(256) void k_gauss_init(GaussFitArgs a, const double
   const double* v0 = init + (size_t)p * npar;
   const int* fl = flags + (size_t)p * npar;
   if (tid < npar) {
-    const int kind = gf_kind(tid, npar);
+    const int kind = gf_kind<JOIN>(tid, npar, a.ngauss);
     const double x = gf_to_int(kind, v0[tid], a.wid_max);
     st[kGfXt + tid] = x;
     st[kGfXi + tid] = x;
@@ -375,6 +435,7 @@ constexpr int kGfInFlight = 16;  // channels whose loads one thread of the chann
 
 // grid (nport).  fit == 0: chi^2, J^T r, J^T J over the external parameters
 // at a.pext into the outputs.  fit == 1: one Levenberg-Marquardt iteration.
+template <bool JOIN>
 __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
   const int p = blockIdx.x, tid = threadIdx.x;
   if (fit && a.state[p].done) return;
@@ -382,7 +443,8 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
   __shared__ double s_fac[kGfMaxPar], s_v[kGfMaxPar], s_x[kGfMaxPar], s_d[kGfMaxPar];
   __shared__ int s_fi[kGfMaxPar], s_free[kGfMaxPar];
   __shared__ double s_red[8];
-  const int npar = a.npar, nchan = a.nchan, KB = 3 * a.ngauss + 3, npairs = KB * (KB + 1) / 2;
+  const int npar = a.npar, nchan = a.nchan, KB = 3 * a.ngauss + 3 + (JOIN ? 1 : 0);
+  const int npairs = KB * (KB + 1) / 2;
   const double* G = a.gram + (size_t)p * nchan * npairs;
   const double* cf = a.coef + (size_t)p * nchan * npar;
   double* st = a.lm + (size_t)p * kGfLmDoubles;
@@ -396,7 +458,8 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
         if (fl[q]) s_free[c++] = q;
       }
     }
-    if (tid < npar) s_fac[tid] = gf_dext(gf_kind(tid, npar), st[kGfXt + tid], a.wid_max);
+    if (tid < npar)
+      s_fac[tid] = gf_dext(gf_kind<JOIN>(tid, npar, a.ngauss), st[kGfXt + tid], a.wid_max);
     __syncthreads();
     nf = a.state[p].nfree;
   }
@@ -417,7 +480,7 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
         ir = s_fi[r];
         if (iq < 0 || ir < 0) continue;
       }
-      const int bq = gf_basis(q, npar), br = gf_basis(r, npar);
+      const int bq = gf_basis<JOIN>(q, npar, a.ngauss), br = gf_basis<JOIN>(r, npar, a.ngauss);
       const int gi = gf_tri(max(bq, br), min(bq, br));
       // kGfInFlight channels' loads in flight, added in channel order
       double s = 0.0;
@@ -440,7 +503,7 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
     } else if (e < ntri + npar) {
       const int q = e - ntri;
       if (fit && s_fi[q] < 0) continue;
-      const int gi = gf_tri(gf_basis(q, npar), 0);
+      const int gi = gf_tri(gf_basis<JOIN>(q, npar, a.ngauss), 0);
       double s = 0.0;
       for (int n = 0; n < nchan; ++n) s = fma(cf[(size_t)n * npar + q], G[(size_t)n * npairs + gi], s);
       s = -s;  // r = (data - model) / err: J = -dmodel / err
@@ -550,7 +613,7 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
         const int q = s_free[tid];
         const double x = s_x[tid] + s_v[tid];
         st[kGfXt + q] = x;
-        a.pext[(size_t)p * npar + q] = gf_to_ext(gf_kind(q, npar), x, a.wid_max);
+        a.pext[(size_t)p * npar + q] = gf_to_ext(gf_kind<JOIN>(q, npar, a.ngauss), x, a.wid_max);
       }
     }
   }
@@ -574,7 +637,7 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
   double* eo = a.perrs + (size_t)p * npar;
   double* co = a.cov ? a.cov + (size_t)p * npar * npar : nullptr;
   if (tid < npar) {
-    const int kind = gf_kind(tid, npar);
+    const int kind = gf_kind<JOIN>(tid, npar, a.ngauss);
     const double x = st[kGfXi + tid];
     const double v = fl[tid] ? gf_to_ext(kind, x, a.wid_max) : a.pext[(size_t)p * npar + tid];
     po[tid] = v;
@@ -627,6 +690,26 @@ __global__ __launch_bounds__(256) void k_gauss_step(GaussFitArgs a, int fit) {
     info[2] = S.dof;
     info[3] = S.nfree;
   }
+}
+
+// The no-join kernels first and in the order they always had in the code
+// object, then what the joint fits add.
+template __global__ void k_gauss_basis<false>(GaussFitArgs);
+template __global__ void k_gauss_gram<false>(GaussFitArgs);
+template __global__ void k_gauss_init<false>(GaussFitArgs, const double*, const int*);
+template __global__ void k_gauss_step<false>(GaussFitArgs, int);
+template __global__ void k_gauss_basis<true>(GaussFitArgs);
+template __global__ void k_gauss_gram<true>(GaussFitArgs);
+template __global__ void k_gauss_init<true>(GaussFitArgs, const double*, const int*);
+template __global__ void k_gauss_step<true>(GaussFitArgs, int);
+
+// grid (ceil(nrow / 256)): *bad = 1 when a row's join group is outside
+// 0 .. njoin - 1 (every writer stores the same value)
+__global__ __launch_bounds__(256) void k_gauss_join_check(const int* __restrict__ join_of,
+                                                          int64_t nrow, int njoin,
+                                                          int* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < nrow && (join_of[i] < 0 || join_of[i] >= njoin)) *bad = 1;
 }
 
 }  // namespace ppf

@@ -731,9 +731,10 @@ struct PcaState {
 
 // Gaussian-component portrait fits (ppfit_gauss.hip).  External parameters
 // of one portrait: DC, tau [bin], per component loc, dloc, wid, dwid, amp,
-// damp, then the scattering index alpha.
-constexpr int kFitMaxGauss = 16, kFitMaxChan = 2048;
-constexpr int kGfMaxPar = 3 + 6 * kFitMaxGauss;  // 99
+// damp, then (joint fits of several receivers) per join group phase_g [rot],
+// DM_g, then the scattering index alpha.
+constexpr int kFitMaxGauss = 16, kFitMaxChan = 2048, kFitMaxJoin = 8;
+constexpr int kGfMaxPar = 3 + 6 * kFitMaxGauss;  // 99, join parameters included
 struct GaussFitState {
   int done;    // no further iterations
   int status;  // PPF_GAUSS_* once done
@@ -752,8 +753,9 @@ constexpr int kGfHc = 520, kGfHt = kGfHc + 10000, kGfLmDoubles = kGfHt + 10000;
 constexpr int kGfChi2 = 0, kGfChi2t = 1, kGfLambda = 2, kGfNu = 3, kGfPred = 4, kGfPnorm = 5,
               kGfXnorm = 6;
 struct GaussFitArgs {
-  int nchan, nbin, ngauss, npar;  // npar = 3 + 6 ngauss
+  int nchan, nbin, ngauss, npar;  // npar = 3 + 6 ngauss + 2 njoin
   int max_nfev;                   // 0: 2000 (nfree + 1)
+  int njoin;                      // join groups (0: one receiver); in the padding before fwhm
   double fwhm, sqrt2pi;           // 2 sqrt(2 ln 2), sqrt(2 pi) as numpy forms them
   double wid_max, ftol, xtol;
   const double* freqs;    // [nport][nchan]
@@ -767,7 +769,7 @@ struct GaussFitArgs {
   const double2* dspec;   // [nport][nchan][nbin / 2 + 1] data spectra
   double* coef;           // [nport][nchan][npar] chain-rule scalars
   double* taun;           // [nport][nchan] tau_n [rot]
-  double* gram;           // [nport][nchan][K (K + 1) / 2], K = 3 ngauss + 3
+  double* gram;           // [nport][nchan][K (K + 1) / 2], K = 3 ngauss + 3 (+ 1: njoin > 0)
   double* lm;             // [nport][kGfLmDoubles] (fits)
   GaussFitState* state;   // [nport] (fits) or null
   double* chi2;           // [nport]
@@ -777,6 +779,9 @@ struct GaussFitArgs {
   double* perrs;          // [nport][npar] (fits)
   double* cov;            // [nport][npar][npar] or null (fits)
   int* info;              // [nport][4] (fits)
+  // joint fits (njoin > 0); last, so that the fields above keep their offsets
+  const int* join_of;     // [nport][nchan] the join group of a row
+  const double* dm_coef;  // [nport][nchan] d theta_n / d DM_g
 };
 
 constexpr int kMaxIrf = 16;
@@ -872,10 +877,12 @@ __global__ void k_fake_gen(FakeArgs a, const double2* tw, int nbin);
 __global__ void k_pack(const double* data, int nbin, short* raw, double* scl, double* offs,
                        int* bad);
 __global__ void k_gauss_port(GaussArgs g, const double* freqs, double* out);
-__global__ void k_gauss_basis(GaussFitArgs a);
-__global__ void k_gauss_gram(GaussFitArgs a);
+template <bool JOIN> __global__ void k_gauss_basis(GaussFitArgs a);
+template <bool JOIN> __global__ void k_gauss_gram(GaussFitArgs a);
+__global__ void k_gauss_join_check(const int* join_of, int64_t nrow, int njoin, int* bad);
+template <bool JOIN>
 __global__ void k_gauss_init(GaussFitArgs a, const double* init, const int* flags);
-__global__ void k_gauss_step(GaussFitArgs a, int fit);
+template <bool JOIN> __global__ void k_gauss_step(GaussFitArgs a, int fit);
 template <typename T>
 __global__ void k_unpack(const T* raw, const double* scl, const double* offs, int nsub, int npol,
                          int nchan, int nbin, int pmode, double* out);

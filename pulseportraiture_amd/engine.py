@@ -726,7 +726,7 @@ class Engine:
         return (out.reshape(r.shape), lev.reshape(lead), fa.reshape(lead), rc.reshape(lead),
                 zeroed.reshape(lead), tab.reshape(lead + (L,)) if table else None)
 
-    def _gauss_inputs(self, data, freqs, errs, params, model_codes, nu_refs):
+    def _gauss_inputs(self, data, freqs, errs, params, model_codes, nu_refs, njoin=0):
         dev = self.device
         x = _dev_f64(data, dev)
         nchan, nbin = int(x.shape[-2]), int(x.shape[-1])
@@ -737,8 +737,9 @@ class Engine:
         par = _dev_f64(params, dev)
         npar = int(par.shape[-1])
         par = par.reshape(-1, npar).expand(nport, npar).contiguous()
-        if (npar - 3) % 6 or npar < 9:
-            raise PPFitError("%d parameters: DC, tau, 6 per component and alpha" % npar)
+        if (npar - 3 - 2 * njoin) % 6 or npar - 2 * njoin < 9:
+            raise PPFitError("%d parameters: DC, tau, 6 per component%s and alpha" % (
+                npar, ", 2 per join group (%d)" % njoin if njoin else ""))
         if isinstance(model_codes, str):
             model_codes = [model_codes] * nport
         code = _dev_i32(np.array([[int(c) for c in str(mc)[:3]] for mc in model_codes],
@@ -793,6 +794,62 @@ class Engine:
             _ptr(out["params"]), _ptr(out["param_errs"]), _ptr(out["cov"]), _ptr(out["chi2"]),
             _ptr(out["info"])))
         out["params"]._keep = (x, f, e, par, fl, code, nu)
+        return out
+
+    def _join_inputs(self, join_of, dm_coef, nport, nchan):
+        dev = self.device
+        jo = join_of if isinstance(join_of, torch.Tensor) else torch.as_tensor(np.asarray(join_of))
+        jo = jo.to(device=dev, dtype=torch.int32).reshape(-1, nchan).expand(
+            nport, nchan).contiguous()
+        dm = _dev_f64(dm_coef, dev).reshape(-1, nchan).expand(nport, nchan).contiguous()
+        return jo, dm
+
+    def gauss_eval_join(self, data, freqs, errs, params, model_codes, nu_refs, join_of, dm_coef,
+                        njoin):
+        """gauss_eval for joint fits of several receivers (ppf_gauss_eval_join):
+        params [nport, npar = 3 + 6 ngauss + 2 njoin] carry phase_g, DM_g per
+        join group before alpha; join_of [nport, nchan] is each row's group,
+        dm_coef [nport, nchan] = Dconst (f^-2 - nu_ref^-2) / P."""
+        njoin = int(njoin)
+        x, f, e, par, code, nu, nport, nchan, nbin, npar = self._gauss_inputs(
+            data, freqs, errs, params, model_codes, nu_refs, max(njoin, 0))
+        jo, dm = self._join_inputs(join_of, dm_coef, nport, nchan)
+        dev = self.device
+        chi2 = torch.empty(nport, dtype=torch.float64, device=dev)
+        jtr = torch.empty((nport, npar), dtype=torch.float64, device=dev)
+        jtj = torch.empty((nport, npar, npar), dtype=torch.float64, device=dev)
+        self._chk(self.lib.ppf_gauss_eval_join(
+            self.ctx, nport, nchan, nbin, (npar - 3 - 2 * max(njoin, 0)) // 6, njoin, _ptr(x),
+            _ptr(f), _ptr(e), _ptr(par), _ptr(code), _ptr(nu), _ptr(jo), _ptr(dm), _ptr(chi2),
+            _ptr(jtr), _ptr(jtj)))
+        chi2._keep = (x, f, e, par, code, nu, jo, dm)
+        return chi2, jtr, jtj
+
+    def gauss_fit_join(self, data, freqs, errs, init_params, fit_flags, model_codes, nu_refs,
+                       join_of, dm_coef, njoin, ftol=1.49012e-8, xtol=1.49012e-8, max_nfev=0):
+        """gauss_fit for joint fits of several receivers
+        (ppf_gauss_fit_join_batch); join_of, dm_coef and njoin as
+        gauss_eval_join takes them.  Returns gauss_fit's dict."""
+        njoin = int(njoin)
+        x, f, e, par, code, nu, nport, nchan, nbin, npar = self._gauss_inputs(
+            data, freqs, errs, init_params, model_codes, nu_refs, max(njoin, 0))
+        jo, dm = self._join_inputs(join_of, dm_coef, nport, nchan)
+        dev = self.device
+        fl = _dev_i32(np.broadcast_to(np.asarray(fit_flags) != 0, (nport, npar)), dev) \
+            if not isinstance(fit_flags, torch.Tensor) else \
+            (fit_flags != 0).to(device=dev, dtype=torch.int32).reshape(-1, npar).expand(
+                nport, npar).contiguous()
+        out = {"params": torch.empty((nport, npar), dtype=torch.float64, device=dev),
+               "param_errs": torch.empty((nport, npar), dtype=torch.float64, device=dev),
+               "cov": torch.empty((nport, npar, npar), dtype=torch.float64, device=dev),
+               "chi2": torch.empty(nport, dtype=torch.float64, device=dev),
+               "info": torch.zeros((nport, 4), dtype=torch.int32, device=dev)}
+        self._chk(self.lib.ppf_gauss_fit_join_batch(
+            self.ctx, nport, nchan, nbin, (npar - 3 - 2 * max(njoin, 0)) // 6, njoin, _ptr(x),
+            _ptr(f), _ptr(e), _ptr(par), _ptr(fl), _ptr(code), _ptr(nu), _ptr(jo), _ptr(dm),
+            float(ftol), float(xtol), int(max_nfev), _ptr(out["params"]),
+            _ptr(out["param_errs"]), _ptr(out["cov"]), _ptr(out["chi2"]), _ptr(out["info"])))
+        out["params"]._keep = (x, f, e, par, fl, code, nu, jo, dm)
         return out
 
     def gauss_bank(self, resid, errs, taun, widths, full=False):
@@ -1111,6 +1168,7 @@ def _on_engine_stream(fn):
 
 for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portraits",
               "spline_portraits", "pca_portraits", "pca_project", "gauss_eval", "gauss_fit",
+              "gauss_eval_join", "gauss_fit_join",
               "instrumental_response_rows",
               "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",

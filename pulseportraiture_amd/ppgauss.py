@@ -11,7 +11,11 @@ The interactive GaussianSelector is replaced by an automatic search
 (max_ngauss > 0: pplib.auto_gaussian_profiles, a matched-filter pursuit on
 the device); auto_gauss and init_params remain.
 
-Not here: metafile / joinfile portraits, residplot and the command line.
+A metafile portrait (several receivers' archives; ppspline.DataPortrait) is
+fitted jointly: a phase and a DM offset per archive alongside the components
+(ppf_gauss_fit_join_batch), written to <model_name>.join after every fit.
+
+Not here: residplot and the command line.
 """
 import time
 
@@ -165,7 +169,8 @@ class DataPortrait(ppspline.DataPortrait):
     def _fit_inputs(self):
         """fit_gaussian_portrait's arguments of model_iteration (ppgauss.py:246-250)."""
         return (self.model_code, self.portx, self.model_params, self.scattering_index,
-                self.noise_stdsxs, self.fit_flags, not self.fixalpha, self.freqsxs[0], self.nu_ref)
+                self.noise_stdsxs, self.fit_flags, not self.fixalpha, self.freqsxs[0], self.nu_ref,
+                self.all_join_params, self.Ps[0])
 
     def _take_fit(self, fgp, duration):
         """model_iteration after the fit (ppgauss.py:251-275)."""
@@ -174,11 +179,19 @@ class DataPortrait(ppspline.DataPortrait):
         self.scattering_index, self.scattering_index_err = (fgp.scattering_index,
                                                             fgp.scattering_index_err)
         self.fgp = fgp
-        self.model_params = self.fitted_params[:]
-        self.model_param_errs = self.fit_errs[:]
+        if self.njoin:
+            self.model_params = self.fitted_params[:-self.njoin * 2]
+            self.model_param_errs = self.fit_errs[:-self.njoin * 2]
+            self.join_params = self.fitted_params[-self.njoin * 2:]
+            self.join_param_errs = self.fit_errs[-self.njoin * 2:]
+            self.all_join_params[1] = self.join_params
+            self.write_join_parameters()
+        else:
+            self.model_params = self.fitted_params[:]
+            self.model_param_errs = self.fit_errs[:]
         self.model = pplib.gen_gaussian_portraits_device(
             self.model_code, self.fitted_params, self.scattering_index, self.nbin, self.freqs[0],
-            self.nu_ref)
+            self.nu_ref, self.join_ichans, self.Ps[0])
         self.model_masked = self.model * self.masks[0, 0]
         self.modelx = np.compress(self.masks[0, 0].mean(axis=1), self.model, axis=0)
         self.duration = duration
@@ -195,7 +208,12 @@ class DataPortrait(ppspline.DataPortrait):
         model, are within their errors times efac (ppgauss.py:278-334).  As
         there: 1, or a falsy value (0 when the phase is outside, None when
         only the DM is)."""
-        portx, modelx = np.copy(self.portx), np.copy(self.modelx)
+        if self.njoin:  # both without the fitted join rotations
+            portx, modelx = (pplib.rotate_join_rows(rows, self.join_ichanxs, self.join_params,
+                                                    self.Ps[0], self.freqsxs[0], self.nu_ref, -1.0)
+                             for rows in (self.portx, self.modelx))
+        else:
+            portx, modelx = np.copy(self.portx), np.copy(self.modelx)
         phase_guess = fit_phase_shift(portx.mean(axis=0), modelx.mean(axis=0)).phase % 1
         if phase_guess >= 0.5:
             phase_guess -= 1.0
@@ -248,8 +266,11 @@ def _fit_batch(dps, quiet):
     start = time.time()
     args = [dp._fit_inputs() for dp in dps]
     cols = list(zip(*args))
+    joined = dps[0].njoin > 0
     fgps = fit_gaussian_portraits(cols[0], cols[1], cols[2], cols[3], cols[4], cols[5], cols[6],
-                                  dps[0].phases, cols[7], cols[8], quiet=quiet)
+                                  dps[0].phases, cols[7], cols[8],
+                                  join_params=cols[9] if joined else [],
+                                  Ps=cols[10] if joined else None, quiet=quiet)
     duration = (time.time() - start) / len(dps)
     for dp, fgp in zip(dps, fgps):
         dp._take_fit(fgp, duration)
@@ -262,7 +283,8 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
                          writeerrfile=False, errfiles=None, model_names=None, residplot=None,
                          quiet=False, init_params=None, max_ngauss=0):
     """make_gaussian_model for a list of DataPortraits whose unzapped
-    portraits share one shape and component count: each iteration's portrait
+    portraits share one shape, component count and number of joined archives
+    (metafile portraits): each iteration's portrait
     fits run in one ppf_gauss_fit_batch call, and with max_ngauss > 0 the
     reference profiles of all portraits that need the component search go
     through one pplib.auto_gaussian_profiles call.  The results are those of
@@ -301,12 +323,12 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
         dp.model_params = np.copy(dp.init_model_params)
         dp.total_time = 0.0
         dp.start = time.time()
-    shape = (dps[0].portx.shape, dps[0].ngauss)
+    shape = (dps[0].portx.shape, dps[0].ngauss, dps[0].njoin)
     for dp in dps:
-        if (dp.portx.shape, dp.ngauss) != shape:
+        if (dp.portx.shape, dp.ngauss, dp.njoin) != shape:
             raise ValueError("make_gaussian_models: portraits of %s and %s (unzapped channels x "
-                             "bins, components); one shape per call" % (shape, (dp.portx.shape,
-                                                                                dp.ngauss)))
+                             "bins, components, joined archives); one shape per call"
+                             % (shape, (dp.portx.shape, dp.ngauss, dp.njoin)))
 
     def finish(batch):
         for dp in batch:
@@ -328,12 +350,25 @@ def make_gaussian_models(portraits, modelfiles=None, ref_prof=(None, None), tau=
         for dp in todo:
             if not quiet:
                 print("\n...iteration %d..." % (dp.itern - dp.niter + 1))
+            if dp.njoin:  # the join parameters carry the alignment (ppgauss.py:191)
+                continue
             dp.port = rotate_data(dp.port, dp.phi, dp.DM, dp.Ps[0], dp.freqs[0], dp.nu_fit)
             dp.portx = rotate_data(dp.portx, dp.phi, dp.DM, dp.Ps[0], dp.freqsxs[0], dp.nu_fit)
         _fit_batch(todo, quiet)
         for dp in todo:
             dp.niter -= 1
         finish(todo)
+    for dp in dps:
+        if dp.njoin:  # data and model without the fitted join rotations (ppgauss.py:206-224)
+            args = (dp.join_params, dp.Ps[0])
+            dp.port = pplib.rotate_join_rows(dp.port, dp.join_ichans, *args, dp.freqs[0],
+                                             dp.nu_ref, -1.0)
+            dp.portx = pplib.rotate_join_rows(dp.portx, dp.join_ichanxs, *args, dp.freqsxs[0],
+                                              dp.nu_ref, -1.0)
+            dp.model = pplib.rotate_join_rows(dp.model, dp.join_ichans, *args, dp.freqs[0],
+                                              dp.nu_ref, -1.0)
+            dp.model_masked = dp.model * dp.masks[0, 0]
+            dp.modelx = np.compress(dp.masks[0, 0].mean(axis=1), dp.model, axis=0)
     if not quiet:
         for dp in dps:
             print("")

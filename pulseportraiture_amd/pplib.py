@@ -140,10 +140,15 @@ def evolve_parameter(freqs, nu_ref, parameter, evol_parameter, code):
 
 def gen_gaussian_portrait(model_code, params, scattering_index, phases, freqs, nu_ref,
                           join_ichans=[], P=None):
-    """Frequency-evolving Gaussian portrait, pplib.py:853-930."""
-    if len(join_ichans):
-        raise NotImplementedError("join_ichans is ppgauss-only (out of scope)")
+    """Frequency-evolving Gaussian portrait, pplib.py:853-930.  With
+    join_ichans (lists of channels, one per receiver) the last 2 len(join_ichans)
+    entries of params are a phase [rot] and a DM per list, by which its rows
+    are rotated as rotate_data does it (numpy's rfft on the host); P [sec] is
+    needed then."""
     params = np.asarray(params, dtype=float)
+    njoin = len(join_ichans)
+    if njoin:
+        join_params, params = params[-2 * njoin:], params[:-2 * njoin]
     ref = np.array([params[0], params[1] * 0.0] + list(params[2::2]))
     tau = params[1]
     nbin, nchan = len(phases), len(freqs)
@@ -160,7 +165,66 @@ def gen_gaussian_portrait(model_code, params, scattering_index, phases, freqs, n
         # and returns nbin - 1 bins at odd nbin); the same for even nbin
         port = np.fft.irfft(scattering_portrait_FT(taus, nbin) *
                             np.fft.rfft(port, axis=-1), n=nbin, axis=-1)
+    for ij in range(njoin):
+        ic = np.asarray(join_ichans[ij], dtype=int)
+        theta = join_rotations(join_params[2 * ij], join_params[2 * ij + 1], P,
+                               np.asarray(freqs, dtype=float)[ic], nu_ref)
+        phasor = np.exp(2.0j * np.pi * np.outer(theta, np.arange(nbin // 2 + 1)))
+        port[ic] = np.fft.irfft(np.fft.rfft(port[ic], axis=-1) * phasor, n=nbin, axis=-1)
     return port
+
+
+def join_dm_coef(P, freqs, nu_ref):
+    """d theta / d DM of a row at freqs: Dconst (f^-2 - nu_ref^-2) / P [rot per
+    cm**-3 pc] (rotate_data, pplib.py:2389-2413)."""
+    return Dconst * (np.asarray(freqs, dtype=float) ** -2.0 - nu_ref ** -2.0) / P
+
+
+def join_rotations(phase, DM, P, freqs, nu_ref):
+    """The rotation [rot] rotate_data(rows, phase, DM, P, freqs, nu_ref) applies
+    to each row."""
+    freqs = np.asarray(freqs, dtype=float)
+    if DM == 0.0:
+        return np.full(len(freqs), float(phase))
+    return phase + Dconst * DM / P * (freqs ** -2.0 - nu_ref ** -2.0)
+
+
+def join_groups(join_ichans, nchan):
+    """join_of [nchan]: the index of the list in join_ichans that holds each
+    channel.  The device fit takes one group per row: channels in no list
+    (left unrotated by the reference) or in several are refused."""
+    join_of = np.full(nchan, -1, dtype=np.int32)
+    count = np.zeros(nchan, dtype=int)
+    for ij, ic in enumerate(join_ichans):
+        ic = np.asarray(ic, dtype=int)
+        join_of[ic] = ij
+        np.add.at(count, ic, 1)
+    if np.any(count != 1):
+        raise NotImplementedError("join_params whose lists do not hold every channel exactly "
+                                  "once are not supported: the device fit takes one join group "
+                                  "per row")
+    return join_of
+
+
+def join_row_rotations(join_ichans, join_params, P, freqs, nu_ref):
+    """The rotation [rot] of every row of a portrait at freqs [nchan] under the
+    join parameters (phase_g, DM_g per list of join_ichans); 0 for a channel
+    in no list."""
+    freqs = np.asarray(freqs, dtype=float)
+    theta = np.zeros(len(freqs))
+    for ij, ic in enumerate(join_ichans):
+        ic = np.asarray(ic, dtype=int)
+        theta[ic] = join_rotations(join_params[2 * ij], join_params[2 * ij + 1], P, freqs[ic],
+                                   nu_ref)
+    return theta
+
+
+def rotate_join_rows(rows, join_ichans, join_params, P, freqs, nu_ref, sign=1.0):
+    """rows [nchan, nbin] with the channels of join_ichans[g] rotated as
+    rotate_data(rows, sign phase_g, sign DM_g, P, freqs, nu_ref) does it, in
+    one device call (ppf_rotate_rows)."""
+    theta = sign * join_row_rotations(join_ichans, join_params, P, freqs, nu_ref)
+    return _engine().rotate_rows(np.asarray(rows, dtype=np.float64), theta).cpu().numpy()
 
 
 def read_model(modelfile, phases=None, freqs=None, P=None, quiet=False):
@@ -220,13 +284,27 @@ def read_model(modelfile, phases=None, freqs=None, P=None, quiet=False):
     return (name, ngauss, model)
 
 
-def gen_gaussian_portraits_device(model_code, params, scattering_index, nbin, freqs, nu_ref):
+def gen_gaussian_portraits_device(model_code, params, scattering_index, nbin, freqs, nu_ref,
+                                  join_ichans=[], P=None):
     """gen_gaussian_portrait (pplib.py:853-930) for rows of frequencies
     ([..., nchan]) in one device call (ppf_gaussian_portraits); returns a
-    numpy array [..., nchan, nbin].  params[1] (TAU) in bins, as there."""
+    numpy array [..., nchan, nbin].  params[1] (TAU) in bins, as there.  With
+    join_ichans the rows are then rotated by the join parameters at the end
+    of params (ppf_rotate_rows)."""
     from .engine import get_engine
-    return get_engine().gaussian_portraits(model_code, params, scattering_index, nbin, freqs,
-                                           nu_ref).cpu().numpy()
+    eng = get_engine()
+    njoin = len(join_ichans)
+    if not njoin:
+        return eng.gaussian_portraits(model_code, params, scattering_index, nbin, freqs,
+                                      nu_ref).cpu().numpy()
+    params = np.asarray(params, dtype=float)
+    join_params, params = params[-2 * njoin:], params[:-2 * njoin]
+    freqs = np.asarray(freqs, dtype=float)
+    port = eng.gaussian_portraits(model_code, params, scattering_index, nbin, freqs, nu_ref)
+    theta = np.array([join_row_rotations(join_ichans, join_params, P, f, nu_ref)
+                      for f in freqs.reshape(-1, freqs.shape[-1])])
+    out = eng.rotate_rows(port.reshape(-1, nbin), theta.ravel())
+    return out.cpu().numpy().reshape(freqs.shape + (nbin,))
 
 
 def read_model_device(modelfile, nbin, freqs, P=None, quiet=False):
@@ -261,7 +339,7 @@ def _row_errs(errs, shape):
     return e[..., 0].copy()
 
 
-def _gauss_bunch(out, i, quiet, title):
+def _gauss_bunch(out, i, quiet, title, njoin=0):
     from ._lib import GAUSS_STATUS
     status, nfev, dof = (int(v) for v in out["info"][i, :3])
     params, errs = out["params"][i], out["param_errs"][i]
@@ -273,10 +351,11 @@ def _gauss_bunch(out, i, quiet, title):
         print(title)
         print("---------------------------------------------------------------")
         print("status:", lm.message)
-        print("Gaussians:", (len(params) - 3) // 6)
+        print("Gaussians:", (len(params) - 3 - 2 * njoin) // 6)
         print("DoF:", dof)
         print("reduced chi-sq: %.2g" % (chi2 / dof))
         print("---------------------------------------------------------------")
+    # (with join parameters fitted_params ends with them, pplib.py:2024-2031)
     return DataBunch(lm_results=lm, fitted_params=params[:-1].copy(), fit_errs=errs[:-1].copy(),
                      scattering_index=params[-1], scattering_index_err=errs[-1], chi2=chi2,
                      dof=dof)
@@ -287,9 +366,18 @@ def fit_gaussian_portraits(model_codes, datas, init_params, scattering_indices, 
                            Ps=None, quiet=True, ftol=1.49012e-8, xtol=1.49012e-8, max_nfev=0):
     """fit_gaussian_portrait for a list of portraits of one shape in one
     device call (ppf_gauss_fit_batch): every argument but phases is a list
-    (or an array with a leading portrait axis).  Returns a list of DataBunch."""
+    (or an array with a leading portrait axis).  Returns a list of DataBunch.
+
+    join_params: one [join_ichanxs, params, flags] per portrait (the
+    reference's, pplib.py:1992-2001) with the same number of lists of channels
+    in each, and Ps the periods [sec]: a joint fit of several receivers
+    (ppf_gauss_fit_join_batch).  fitted_params and fit_errs then end with the
+    2 njoin join entries."""
     if len(join_params):
-        raise NotImplementedError("join_params (joinfile portraits) are not supported")
+        return _fit_gaussian_portraits_join(
+            model_codes, datas, init_params, scattering_indices, errs, fit_flags,
+            fit_scattering_indices, phases, freqs, nu_refs, join_params, Ps, quiet, ftol, xtol,
+            max_nfev)
     n = len(datas)
     data = np.stack([np.asarray(d, dtype=np.float64) for d in datas])
     if data.ndim != 3 or data.shape[-1] != len(phases):
@@ -306,6 +394,38 @@ def fit_gaussian_portraits(model_codes, datas, init_params, scattering_indices, 
     return [_gauss_bunch(out, i, quiet, "Gaussian Portrait Fit") for i in range(n)]
 
 
+def _fit_gaussian_portraits_join(model_codes, datas, init_params, scattering_indices, errs,
+                                 fit_flags, fit_scattering_indices, phases, freqs, nu_refs,
+                                 join_params, Ps, quiet, ftol, xtol, max_nfev):
+    """fit_gaussian_portraits with join parameters."""
+    n = len(datas)
+    if len(join_params) != n:
+        raise ValueError("join_params: one [join_ichanxs, params, flags] per portrait")
+    njoin = len(join_params[0][0])
+    if any(len(jp[0]) != njoin for jp in join_params):
+        raise ValueError("one number of join groups per call")
+    data = np.stack([np.asarray(d, dtype=np.float64) for d in datas])
+    if data.ndim != 3 or data.shape[-1] != len(phases):
+        raise ValueError("portraits of one shape [nchan, nbin = len(phases)] per call")
+    nchan = data.shape[1]
+    join_of = np.stack([join_groups(jp[0], nchan) for jp in join_params])
+    if Ps is None or len(Ps) != n or any(P is None for P in Ps):
+        raise ValueError("join_params need the period P [sec] of every portrait")
+    fr = np.stack([np.asarray(f, dtype=np.float64) for f in freqs])
+    par = np.array([np.concatenate([np.asarray(p, dtype=np.float64),
+                                    np.asarray(jp[1], dtype=np.float64), [float(a)]])
+                    for p, jp, a in zip(init_params, join_params, scattering_indices)])
+    fl = np.array([np.concatenate([np.asarray(f) != 0, np.asarray(jp[2]) != 0, [bool(fa)]])
+                   for f, jp, fa in zip(fit_flags, join_params, fit_scattering_indices)])
+    er = np.stack([_row_errs(e, data.shape[1:]) for e in errs])
+    dm_coef = np.stack([join_dm_coef(P, f, nu) for P, f, nu in zip(Ps, fr, nu_refs)])
+    out = _engine().gauss_fit_join(data, fr, er, par, fl, [str(c) for c in model_codes],
+                                   np.asarray(nu_refs, dtype=np.float64), join_of, dm_coef, njoin,
+                                   ftol, xtol, max_nfev)
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    return [_gauss_bunch(out, i, quiet, "Gaussian Portrait Fit", njoin) for i in range(n)]
+
+
 def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs, fit_flags,
                           fit_scattering_index, phases, freqs, nu_ref, join_params=[], P=None,
                           quiet=True):
@@ -313,10 +433,14 @@ def fit_gaussian_portrait(model_code, data, init_params, scattering_index, errs,
     the device: lmfit's leastsq with its bounds (tau >= 0, 0 <= wid <=
     wid_max, amp >= 0) and an analytic Jacobian.  Returns the reference's
     DataBunch; lm_results is a record of status, message, nfev, covar and
-    success.  errs [nchan, nbin] has to be constant along each row."""
+    success.  errs [nchan, nbin] has to be constant along each row.
+    join_params = [join_ichanxs, params, flags] and the period P [sec] fit a
+    phase and a DM per list of channels alongside (pplib.py:1992-2001)."""
+    joined = len(join_params) > 0
     return fit_gaussian_portraits([model_code], [data], [init_params], [scattering_index], [errs],
                                   [fit_flags], [fit_scattering_index], phases, [freqs], [nu_ref],
-                                  join_params, None, quiet)[0]
+                                  [join_params] if joined else [], [P] if joined else None,
+                                  quiet)[0]
 
 
 def profile_fit_flags(nparam, fit_flags=None, fit_scattering=False):

@@ -18,7 +18,11 @@ PyWavelets' output, which is not available to pin against.  Without smoothing
 large nbin, so callers should pass smooth="swt" or set max_ncomp
 (INTEGRATION.md).
 
-Not here: metafile / joinfile portraits, plotting and the command line.
+A metafile (an ASCII list of archives, one per receiver) gives the
+reference's concatenated portrait (pplib.py:163-299) with its join attributes,
+which ppgauss fits; make_spline_model takes it as it is.
+
+Not here: plotting and the command line.
 """
 import pickle
 
@@ -67,19 +71,57 @@ def fit_spline_curve(proj_port, weights, freqs, s, bw=1.0, k=3, max_nbreak=None,
     return (tck, u_out), fp, ier, msg
 
 
+JOIN_HEADER = ("# archive name" + " " * 32 + "-phase offset & err [rot]" + " " * 2 +
+               "-delta-DM & err [cm**-3 pc]\n")
+
+
+def join_parameter_line(datafile, phase, phase_err, dm, dm_err):
+    """One line of a .join file (pplib.py:516-519)."""
+    return (datafile + " " * abs(45 - len(datafile)) + "% .10f" % phase + " " * 1 +
+            "%.10f" % phase_err + " " * 2 + "% .6f" % dm + " " * 1 + "%.6f" % dm_err + "\n")
+
+
+def read_joinfile(joinfile, datafiles, join_params):
+    """join_params with the phases and DMs of a .join file's last
+    len(datafiles) lines, matched by archive name (pplib.py:282-297): the
+    columns are name, phase, phase error, DM, DM error, or (old files) name,
+    phase, DM."""
+    join_params = np.array(join_params, dtype=np.float64)
+    with open(joinfile, "r") as jf:
+        lines = [line.split() for line in jf.readlines()[-len(datafiles):]]
+    try:
+        for line in lines:
+            ijoin = datafiles.index(line[0])
+            join_params[ijoin * 2] = np.double(line[1])
+            join_params[ijoin * 2 + 1] = np.double(line[3] if len(line) > 3 else line[2])
+    except (ValueError, IndexError):
+        print("Bad join file.")
+    return join_params
+
+
 class DataPortrait(object):
-    """The data to which a model is fitted (pplib.py:139-327, one archive): a
-    PSRFITS file, an .npz, or a registered / dict archive, loaded dedispersed,
-    tscrunched and pscrunched.  port is the masked portrait, portx its
-    unzapped channels; likewise freqs / freqsxs, noise_stds / noise_stdsxs
-    and SNRs / SNRsxs."""
+    """The data to which a model is fitted (pplib.py:139-327): a PSRFITS
+    file, an .npz, or a registered / dict archive, loaded dedispersed,
+    tscrunched and pscrunched -- or a metafile, an ASCII list of such
+    archives (one per receiver), whose rows are concatenated and sorted by
+    frequency.  port is the masked portrait, portx its unzapped channels;
+    likewise freqs / freqsxs, noise_stds / noise_stdsxs and SNRs / SNRsxs.
+
+    For a metafile join_ichans / join_ichanxs hold each archive's rows of
+    port / portx, join_params its phase [rot] and DM offsets (the first
+    archive's phase 0 and fixed, the others' from fit_phase_shift against the
+    first's profile; every DM 0 and free) or those of joinfile, and
+    all_join_params = [join_ichanxs, join_params, join_fit_flags] is what
+    pplib.fit_gaussian_portrait takes."""
 
     def __init__(self, datafile, quiet=False, joinfile=None):
-        if joinfile is not None:
-            raise NotImplementedError("joinfile portraits are not supported")
+        self.joinfile = joinfile
         if _arch.file_is_type(datafile, "ASCII"):
-            raise NotImplementedError("metafile portraits are not supported: %s lists archives; "
-                                      "give one averaged archive" % datafile)
+            self._load_metafile(datafile, quiet)
+            return
+        if joinfile is not None:
+            raise NotImplementedError("joinfile: only with a metafile (one archive has nothing "
+                                      "to join)")
         self.njoin = 0
         self.join_params, self.join_ichans, self.all_join_params = [], [], []
         self.data = _arch.load_data(datafile, dedisperse=True, dededisperse=False, tscrunch=True,
@@ -107,6 +149,144 @@ class DataPortrait(object):
         self.noise_stdsxs = self.noise_stds[0, 0, ok]
         self.SNRsxs = self.SNRs[0, 0, ok]
         self.norm_values = np.ones(len(self.port))
+
+    def _load_metafile(self, metafile, quiet):
+        """The concatenated portrait of a metafile's archives (pplib.py:163-299)."""
+        with open(metafile, "r") as mf:
+            self.datafiles = [line.strip() for line in mf.readlines() if line.strip()]
+        self.metafile = self.datafile = metafile
+        self.njoin = len(self.datafiles)
+        for datafile in self.datafiles:
+            if not _arch.file_is_type(datafile, "FITS"):
+                raise NotImplementedError(
+                    "metafile %s lists %s, which is not a registered, .npz or PSRFITS archive: "
+                    "archives in other PSRCHIVE formats are not supported" % (metafile, datafile))
+        join_params, join_fit_flags = [], []
+        join_nchans, join_nchanxs = [0], [0]
+        cols = {key: [] for key in ("freqs", "freqsxs", "masks", "port", "portx", "noise_stds",
+                                    "noise_stdsxs", "SNRs", "SNRsxs", "weights", "weightsxs")}
+        Ps, lofreq, hifreq = 0.0, np.inf, 0.0
+        for ifile, datafile in enumerate(self.datafiles):
+            data = _arch.load_data(datafile, dedisperse=True, tscrunch=True, pscrunch=True,
+                                   fscrunch=False, flux_prof=True, return_arch=True, quiet=quiet)
+            sub = _arch.host_array(data.subints)[0, 0]
+            ok = np.asarray(data.ok_ichans[0])
+            weights = np.asarray(data.weights, dtype=np.float64)[0]
+            masks = np.asarray(data.masks)[0, 0]
+            noise = get_noise(sub, chans=True) if data.noise_stds is None else \
+                np.asarray(data.noise_stds, dtype=np.float64)[0, 0]
+            SNRs = np.asarray(data.SNRs, dtype=np.float64)[0, 0]
+            # the archive's fscrunched profile (weighted, as PSRCHIVE scrunches)
+            prof = np.average(sub[ok], axis=0, weights=weights[ok])
+            if ifile == 0:
+                self.nbin, self.phases, self.source = data.nbin, data.phases, data.source
+                refprof = prof
+                join_params += [0.0, 0.0]
+                join_fit_flags += [0, 1]
+            else:
+                if data.nbin != self.nbin:
+                    raise ValueError("%s: %s has %d phase bins and %s has %d; a joint portrait "
+                                     "needs one nbin" % (metafile, datafile, data.nbin,
+                                                         self.datafiles[0], self.nbin))
+                phi = -pplib.fit_phase_shift(prof, refprof, Ns=self.nbin).phase
+                join_params += [phi, 0.0]
+                join_fit_flags += [1, 1]
+            join_nchans.append(join_nchans[-1] + data.nchan)
+            join_nchanxs.append(join_nchanxs[-1] + len(ok))
+            Ps += np.mean(data.Ps)
+            half = abs(data.bw) / (2 * data.nchan)
+            lofreq = min(lofreq, data.freqs.min() - half)
+            hifreq = max(hifreq, data.freqs.max() + half)
+            cols["freqs"].extend(data.freqs[0])
+            cols["freqsxs"].extend(data.freqs[0, ok])
+            cols["masks"].extend(masks)
+            cols["port"].extend(sub * masks)
+            cols["portx"].extend(sub[ok])
+            cols["noise_stds"].extend(noise)
+            cols["noise_stdsxs"].extend(noise[ok])
+            cols["SNRs"].extend(SNRs)
+            cols["SNRsxs"].extend(SNRs[ok])
+            cols["weights"].extend(weights)
+            cols["weightsxs"].extend(weights[ok])
+        if self.source is None:
+            self.source = "noname"
+        self.Ps = [Ps / self.njoin]
+        self.lofreq, self.hifreq = lofreq, hifreq
+        self.bw = hifreq - lofreq
+        freqs, freqsxs = np.array(cols["freqs"]), np.array(cols["freqsxs"])
+        self.nu0 = freqs.mean()
+        self.isort, self.isortx = np.argsort(freqs), np.argsort(freqsxs)
+        self.join_nchans, self.join_nchanxs = join_nchans, join_nchanxs
+        self.join_ichans = [np.flatnonzero((self.isort >= join_nchans[i]) *
+                                           (self.isort < join_nchans[i + 1]))
+                            for i in range(self.njoin)]
+        self.join_ichanxs = [np.flatnonzero((self.isortx >= join_nchanxs[i]) *
+                                            (self.isortx < join_nchanxs[i + 1]))
+                             for i in range(self.njoin)]
+        self.masks = np.array(cols["masks"])[self.isort][None, None]
+        self.port = np.array(cols["port"])[self.isort]
+        self.portx = np.array(cols["portx"])[self.isortx]
+        self.flux_prof = self.port.mean(axis=1)
+        self.flux_profx = self.portx.mean(axis=1)
+        self.noise_stds = np.array(cols["noise_stds"])[self.isort][None, None]
+        self.noise_stdsxs = np.array(cols["noise_stdsxs"])[self.isortx]
+        self.SNRs = np.array(cols["SNRs"])[self.isort][None, None]
+        self.SNRsxs = np.array(cols["SNRsxs"])[self.isortx]
+        self.weights = np.array(cols["weights"])[self.isort][None]
+        self.weightsxs = np.array(cols["weightsxs"])[self.isortx][None]
+        self.freqs = freqs[self.isort][None]
+        self.freqsxs = [freqsxs[self.isortx]]
+        self.nchan = len(self.port)
+        self.nchanx = len(self.portx)
+        self.ok_ichans = [np.flatnonzero(self.weights[0] > 0.0)]
+        self.norm_values = np.ones(self.nchan)
+        self.join_params = np.array(join_params)
+        self.join_param_errs = np.zeros(len(join_params))
+        self.join_fit_flags = np.array(join_fit_flags)
+        if self.joinfile:
+            self.join_params = read_joinfile(self.joinfile, self.datafiles, self.join_params)
+        self.all_join_params = [self.join_ichanxs, self.join_params, self.join_fit_flags]
+
+    def apply_joinfile(self, nu_ref, undo=False):
+        """Rotate port and portx by minus the join parameters about nu_ref
+        [MHz], the fitted model's reference frequency (pplib.py:329-355);
+        undo=True rotates the other way.
+
+        A rotation drops the imaginary part it gives the Nyquist harmonic, so
+        rotating back does not return the rows it started from (noise has
+        power there).  undo=True therefore puts back the arrays the last
+        apply_joinfile(nu_ref) rotated, when port and portx are still the
+        arrays it left and the join parameters are the same; otherwise it
+        rotates, as the reference does."""
+        sign = 1.0 if undo else -1.0
+        key = (float(nu_ref), tuple(float(v) for v in self.join_params))
+        last = getattr(self, "_joinfile_applied", None)
+        self._joinfile_applied = None
+        if undo and last is not None and last[0] == key and self.port is last[3] \
+                and self.portx is last[4]:
+            self.port, self.portx = last[1], last[2]
+            return
+        before = (self.port, self.portx)
+        self.port = pplib.rotate_join_rows(self.port, self.join_ichans, self.join_params,
+                                           self.Ps[0], self.freqs[0], nu_ref, sign)
+        self.portx = pplib.rotate_join_rows(self.portx, self.join_ichanxs, self.join_params,
+                                            self.Ps[0], self.freqsxs[0], nu_ref, sign)
+        if not undo:
+            self._joinfile_applied = (key,) + before + (self.port, self.portx)
+
+    def write_join_parameters(self):
+        """Append the join parameters to joinfile, or to <model_name>.join
+        (pplib.py:486-521).  As there, the parameters are the opposite of the
+        rotation that aligns the data: use a negative with rotate_data; the
+        DMs are offsets, not Doppler corrected."""
+        joinfile = self.joinfile if self.joinfile is not None else self.model_name + ".join"
+        with open(joinfile, "a") as jf:
+            jf.write(JOIN_HEADER)
+            for ifile, datafile in enumerate(self.datafiles):
+                jf.write(join_parameter_line(datafile, self.join_params[ifile * 2],
+                                             self.join_param_errs[::2][ifile],
+                                             self.join_params[ifile * 2 + 1],
+                                             self.join_param_errs[1::2][ifile]))
 
     def normalize_portrait(self, method="rms"):
         """Normalize each channel's profile (pplib.py:357-382)."""
