@@ -18,6 +18,10 @@
  *                              ppalign.py:202-208
  *   ppf_rotate_accumulate_spec <- the same sum over cached data spectra
  *                              (ppalign.py:202-208, iterations after the first)
+ *   ppf_rotate_fscrunch     <- the dedispersed, weighted fscrunch per unit:
+ *                              arch.fscrunch() in pplib.make_constant_portrait
+ *                              (pplib.py:958-994) and the profiles psradd -P
+ *                              aligns on (ppalign.py:21-38)
  *   ppf_irfft_rows          <- numpy.fft.irfft (final step of ppalign.py:210-213)
  *   ppf_noise_rows          <- pplib.get_noise_PS(chans=True)  pplib.py:2227-2253
  *   ppf_unpack_subints      <- PSRCHIVE Archive_load + pscrunch in
@@ -78,7 +82,7 @@
  *    ppf_fit_portrait_batch, ppf_rotate_rows, ppf_scatter_rotate_rows,
  *    ppf_gaussian_portraits, ppf_spline_portraits,
  *    ppf_instrumental_response_rows, ppf_phase_shift_batch,
- *    ppf_rotate_accumulate, ppf_irfft_rows, ppf_noise_rows and
+ *    ppf_rotate_accumulate, ppf_rotate_fscrunch, ppf_irfft_rows, ppf_noise_rows and
  *    ppf_resid_chi2_rows run direct-sum kernels instead (O(nbin^2) per row;
  *    tests/test_gpu_generic_nbin.py), and so do the data-spectrum cache
  *    (PPF_SPEC_*, ppf_spec_nhp, ppf_rotate_accumulate_spec) and
@@ -133,7 +137,8 @@ extern "C" {
 #define PPF_K_PACK 17
 #define PPF_K_SWT 18
 #define PPF_K_GBANK 19
-#define PPF_NUM_KERNELS 20
+#define PPF_K_FSCRUNCH 20
+#define PPF_NUM_KERNELS 21
 
 typedef struct ppf_ctx ppf_ctx;
 
@@ -428,6 +433,18 @@ int ppf_rotate_accumulate(ppf_ctx* ctx, int32_t nsub, int32_t nchan,
 int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan,
                                int32_t nbin, const double* spec, const double* phase,
                                const double* weight, double* accum);
+
+/* Rotate and frequency-scrunch: for every unit u (an archive or a subint)
+ *   prof[u] = irfft(sum_n weight[u][n] rfft(data[u][n]) e^{2 pi i k phase[u][n]}, n = nbin)
+ * i.e. sum_n weight[u][n] * ppf_rotate_rows(data[u][n], phase[u][n]); data
+ * [nunit][nchan][nbin], phase and weight [nunit][nchan], prof [nunit][nbin].
+ * Channels of weight 0 are skipped; nchan <= 0 gives zeros.  The channels are
+ * summed in a fixed order that does not depend on nunit (slices of a fixed
+ * number of channels, then the slices in order, no atomics): a unit's profile
+ * is bitwise the same alone or among other units, and from run to run.      */
+int ppf_rotate_fscrunch(ppf_ctx* ctx, int32_t nunit, int32_t nchan, int32_t nbin,
+                        const double* data, const double* phase, const double* weight,
+                        double* prof);
 
 /* Gaussian-component template rows (gen_gaussian_portrait, pplib.py:853-930,
  * as read_model calls it, pplib.py:2873-2959): out[r][:] at freqs[r] for

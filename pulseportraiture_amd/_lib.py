@@ -20,7 +20,7 @@ METHODS = {"trust-ncg": PPF_METHOD_TRUST_NCG, "TNC": PPF_METHOD_TNC,
 KERNEL_IDS = {"model_fft": 0, "data_xspec": 1, "solve": 2, "phase_shift": 3,
               "rotate": 4, "rot_accum": 5, "synth": 6, "irfft": 7, "noise": 8,
               "guess": 9, "post": 10, "fit_taylor": 11, "moments": 12, "resid": 13, "unpack": 14,
-              "pca": 15, "gauss": 16, "pack": 17, "swt": 18, "gbank": 19}
+              "pca": 15, "gauss": 16, "pack": 17, "swt": 18, "gbank": 19, "fscrunch": 20}
 PPF_THRESH = {"hard": 0, "soft": 1}
 PPF_SOLVE_EXACT = 1
 PPF_SOLVE_EVAL = 2
@@ -101,6 +101,8 @@ EXPORTS = {
                                ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_rotate_accumulate_spec": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_rotate_fscrunch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                             ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_spec_nhp": ([ctypes.c_int32], ctypes.c_int32),
     "ppf_irfft_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp],
                        ctypes.c_int),

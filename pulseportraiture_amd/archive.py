@@ -367,6 +367,15 @@ def dedispersion_phases(freqs, Ps, DM, nu_ref):
     return Dconst * DM * (f ** -2.0 - nu_ref ** -2.0) / np.asarray(Ps, dtype=np.float64)[:, None]
 
 
+def stored_dedispersion_phases(b):
+    """The rotation [nsub, nchan] load_data(dedisperse=True) applies to the
+    bunch b of an archive loaded as stored: dedispersion_phases about its
+    centre frequency, or none when it is stored dedispersed."""
+    if int(b.get("dmc", 0)):
+        return np.zeros(np.shape(b.weights))
+    return dedispersion_phases(b.freqs, b.Ps, b.DM, b.nu0)
+
+
 class Archive:
     """An opened archive: ``meta`` holds every load_data key but ``subints``
     (after the requested processing); ``read(lo, hi)`` returns processed

@@ -1509,6 +1509,70 @@ int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_
   });
 }
 
+int ppf_rotate_fscrunch(ppf_ctx* ctx, int32_t nunit, int32_t nchan, int32_t nbin,
+                        const double* data, const double* phase, const double* weight,
+                        double* prof) {
+  if (!ctx || !data || !phase || !weight || !prof)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nunit <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (nchan <= 0) {  // an empty sum per unit
+    HIPCHK(ctx, hipMemsetAsync(prof, 0, (size_t)nunit * nbin * sizeof(double), ctx->stream));
+    return PPF_OK;
+  }
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  const int NH = nbin / 2 + 1;
+  // slices of kFsSlice channels whatever the call holds: a unit's profile
+  // is summed in the same order alone or among others
+  const int nslice = (nchan + kFsSlice - 1) / kFsSlice;
+  // per unit: the slices' partial spectra, then the unit's spectrum; units in
+  // chunks under the workspace limit (and one launch's grid)
+  const size_t bPart = (size_t)nslice * NH * sizeof(double2), bSpec = (size_t)NH * sizeof(double2);
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)nunit, ctx->ws_limit / (int64_t)(bPart + bSpec + 512),
+                            (int64_t)0x7fffffff / nslice}));
+  const size_t oSpec = align256((size_t)chunk * bPart);
+  if (int r = ensure(ctx, ctx->buf[kWs], oSpec + (size_t)chunk * bSpec)) return r;
+  double2* partial = reinterpret_cast<double2*>(ctx->buf[kWs].p);
+  double2* spec = reinterpret_cast<double2*>(static_cast<char*>(ctx->buf[kWs].p) + oSpec);
+  const int nyq = (nbin & 1) ? -1 : nbin / 2;
+  const bool wave = logN == 10;  // nbin 2048: the register FFT (2.6x the LDS kernel)
+  for (int64_t u0 = 0; u0 < nunit; u0 += chunk) {
+    const int nu = (int)std::min<int64_t>(chunk, nunit - u0);
+    const double* d = data + (size_t)u0 * nchan * nbin;
+    const double* ph = phase + (size_t)u0 * nchan;
+    const double* w = weight + (size_t)u0 * nchan;
+    const unsigned grid = (unsigned)nu * (unsigned)nslice;
+    const size_t count = (size_t)nu * NH;
+    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          if (logN < 0)
+            hipLaunchKernelGGL(k_fscrunch_gen, dim3(grid), dim3(kBlock), gen_row_lds(nbin),
+                               ctx->stream, d, ph, w, partial, nchan, nslice, tw, nbin);
+          else if (wave)
+            hipLaunchKernelGGL(k_fscrunch_w, dim3(grid), dim3(256), 0, ctx->stream, d, ph, w,
+                               partial, nchan, nslice, tw);
+          else
+            LOGN_SWITCH(logN, hipLaunchKernelGGL(k_fscrunch<LG>, dim3(grid), dim3(kBlock), 0,
+                                                 ctx->stream, d, ph, w, partial, nchan, nslice,
+                                                 tw));
+        }))
+      return r;
+    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          hipLaunchKernelGGL(k_fscrunch_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256),
+                             0, ctx->stream, partial, spec, nslice, NH, nyq, count);
+        }))
+      return r;
+    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          launch_irfft_rows(ctx->stream, logN, nbin, nu, spec, prof + (size_t)u0 * nbin, tw);
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
 int ppf_gaussian_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin, int32_t ngauss,
                            const int32_t* code, const double* params, double nu_ref, double alpha,
                            const double* freqs, double* out) {

@@ -857,6 +857,19 @@ __global__ void k_data_post_gen(SpecArgs a, int nbin);
 __global__ void k_synth_gen(const double2* Mfull, const double* phase, double* data, int nchan,
                             int NHP, double sigma, uint64_t seed, int64_t sub0,
                             const double2* tw, int nbin);
+// ppf_rotate_fscrunch (ppfit_fscrunch.hip): channels per workgroup, a
+// constant of the build (the order of summation may not depend on the call)
+constexpr int kFsSlice = 32;
+template <int LOGN>
+__global__ void k_fscrunch(const double* data, const double* phase, const double* weight,
+                           double2* partial, int nchan, int nslice, const double2* tw);
+__global__ void k_fscrunch_w(const double* data, const double* phase, const double* weight,
+                             double2* partial, int nchan, int nslice, const double2* tw);
+__global__ void k_fscrunch_gen(const double* data, const double* phase, const double* weight,
+                               double2* partial, int nchan, int nslice, const double2* tw,
+                               int nbin);
+__global__ void k_fscrunch_reduce(const double2* partial, double2* spec, int nslice, int NH,
+                                  int nyq, size_t count);
 // ppf_fake_subints / ppf_pack_subints (ppfit_fake.hip)
 struct FakeArgs {
   const double2* M;     // model spectra [nchan][NHP]

@@ -1038,6 +1038,28 @@ class Engine:
                                                  _ptr(w), _ptr(accum)))
         return (d, ph, w)
 
+    def rotate_fscrunch(self, data, phase, weight):
+        """The weighted sum over channels of the rotated rows, per unit
+        (ppf_rotate_fscrunch): data [nunit, nchan, nbin], phase and weight
+        [nunit, nchan] -> [nunit, nbin] float64 device tensor, sum_n weight *
+        rotate_rows(data, phase).  A unit's profile does not depend on the
+        other units of the call (bitwise)."""
+        dev = self.device
+        d = _dev_f64(data, dev)
+        if d.dim() != 3:
+            raise PPFitError("rotate_fscrunch: data [nunit, nchan, nbin]")
+        d = d.contiguous()
+        nunit, nchan, nbin = d.shape
+        ph = _dev_f64(phase, dev).reshape(nunit, nchan).contiguous()
+        w = _dev_f64(weight, dev).reshape(nunit, nchan).contiguous()
+        if nunit == 0 or nchan == 0:  # nothing to sum (an empty tensor has no address to pass)
+            return torch.zeros((nunit, nbin), dtype=torch.float64, device=dev)
+        out = torch.empty((nunit, nbin), dtype=torch.float64, device=dev)
+        self._chk(self.lib.ppf_rotate_fscrunch(self.ctx, nunit, nchan, nbin, _ptr(d), _ptr(ph),
+                                               _ptr(w), _ptr(out)))
+        out._keep = (d, ph, w)
+        return out
+
     def spec_cache(self, nsub, nchan, nbin):
         """An empty data-spectrum cache for fit_batch(spec_cache=...) and
         rotate_accumulate_spec: nsub * nchan * NHP complex spectra (NHP =
@@ -1172,7 +1194,8 @@ for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portrai
               "instrumental_response_rows",
               "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",
-              "scatter_rotate_rows", "rotate_accumulate", "spec_cache", "rotate_accumulate_spec",
+              "scatter_rotate_rows", "rotate_accumulate", "rotate_fscrunch", "spec_cache",
+              "rotate_accumulate_spec",
               "synth", "pack_subints", "fake_subints"):
     setattr(Engine, _name, _on_engine_stream(getattr(Engine, _name)))
 del _name

@@ -804,3 +804,324 @@ def _normalize(port, method, get_noise):
     """normalize_portrait for the final template (pplib.py:2462-2507)."""
     from .pplib import normalize_portrait
     return normalize_portrait(port, method, get_noise=get_noise)
+
+
+# ---------------------------------------------------------------------------
+# The starting template (ppalign.py:21-52, 341-380): the sum of the archives
+# (psradd -T [-P]), a constant portrait, a wavelet-smoothed copy (psrsmooth
+# -W), and the command-line driver that chooses between them.
+# ---------------------------------------------------------------------------
+def _datafiles(metafile):
+    if isinstance(metafile, str) and _arch.file_is_type(metafile, "ASCII"):
+        return [ln.strip() for ln in open(metafile).readlines() if ln.strip()]
+    return list(metafile) if not isinstance(metafile, str) else [metafile]
+
+
+def palign_phases(eng, data, dedisp, weights):
+    """The rotation of every unit that add_archives(palign=True) adds it with:
+    data [nunit, nchan, nbin] (total intensity, device), dedisp and weights
+    [nunit, nchan].  Two batched rounds on the units' profiles p_u =
+    rotate_fscrunch(data, dedisp, weights): (1) against the profile of largest
+    S/N (Engine.profile_snr, the lowest index on a tie), phase_shift_batch;
+    (2) against r = sum_u rotate_rows(p_u, phase_u) of round 1.  The round-2
+    phases, less the reference unit's own, are returned ([nunit], numpy) with
+    the reference unit's index."""
+    nunit, nchan, nbin = data.shape
+    p = eng.rotate_fscrunch(data, dedisp, weights)
+    ustar = int(np.argmax(eng.profile_snr(p).cpu().numpy()))
+    ph1 = eng.phase_shift_batch(p, p[ustar], Ns=nbin)[:, 0]
+    # the sum of the rotated profiles in unit order (one "unit" of nunit rows)
+    r = eng.rotate_fscrunch(p[None], ph1[None], torch.ones_like(ph1)[None])[0]
+    ph2 = eng.phase_shift_batch(p, r, Ns=nbin)[:, 0].cpu().numpy()
+    return ph2 - ph2[ustar], ustar
+
+
+def add_archives(metafile, outfile, palign=False, tscrunch=True, pscrunch=True, quiet=False):
+    """The weighted sum of a metafile's archives as one subint, a starting
+    template for align_archives: the package's stand-in for ``psradd -T [-P]
+    -o outfile -M metafile`` (ppalign.py:21-38).  It is NOT pinned against
+    psradd, which is not available: it is a defined stand-in, meant to be a
+    good starting template, not to match psradd's output.
+
+    The archives are read as stored (load_data: no dedispersion, the baseline
+    removed as align_archives removes it); those that cannot be read, or
+    differ from the first readable one in nchan, nbin, channel frequencies or
+    dedispersed state, are skipped with a note.  A unit is one archive
+    tscrunched (tscrunch=True) or one subint; units with no positive weight
+    are dropped.  palign=False adds every unit with zero phase; palign=True
+    with the phases of palign_phases (two batched rounds; psradd -P keeps a
+    sequential running total).  Then
+
+        out[c] = sum_u w[u, c] rotate(x[u, c], phase_u) / sum_u w[u, c]
+
+    where that weight sum is positive and zeros elsewhere (rotate_accumulate,
+    irfft_rows): one rotation per unit for every channel, so the data stay in
+    the state they were stored in.  pscrunch=False: the phases come from total
+    intensity (the first polarisation) and every polarisation is added with
+    them.  outfile (rank 0 writes it) gets the first archive's tscrunched
+    metadata with its DM and dedispersed flag, one subint, weights 1 or 0.
+    Every unit's data are on the device at once.
+
+    Returns (portrait [npol, nchan, nbin], phases [nunit], weights [nchan]),
+    numpy arrays."""
+    from .engine import get_engine
+    from .pplib import unload_new_archive
+    eng = get_engine()
+    dev = eng.device
+    first = first_name = None
+    data, wts, dds = [], [], []
+    for name in _datafiles(metafile):
+        try:
+            d = _arch.load_data(name, dedisperse=False, dededisperse=False, tscrunch=tscrunch,
+                                pscrunch=pscrunch, rm_baseline=rm_baseline, quiet=True,
+                                host=False)
+        except RuntimeError:
+            if not quiet:
+                print("%s: cannot load_data().  Skipping it." % name)
+            continue
+        if first is None:
+            first, first_name = d, name
+        else:
+            why = None
+            if (d.nchan, d.nbin) != (first.nchan, first.nbin):
+                why = "(%d, %d) != (%d, %d) channels and phase bins" % (
+                    d.nchan, d.nbin, first.nchan, first.nbin)
+            elif d.npol != first.npol:
+                why = "%d != %d polarisations" % (d.npol, first.npol)
+            elif not (np.asarray(d.freqs) == np.asarray(first.freqs)[0]).all():
+                why = "other channel frequencies"
+            elif int(d.dmc) != int(first.dmc):
+                why = "other dedispersed state"
+            if why is not None:
+                print("%s: %s than %s.  Skipping it." % (name, why, first_name))
+                continue
+        w = np.asarray(d.weights, dtype=np.float64)
+        dd = _arch.stored_dedispersion_phases(d)
+        sub = torch.as_tensor(d.subints, dtype=torch.float64, device=dev)
+        for isub in range(d.nsub):
+            if (w[isub] > 0.0).any():
+                data.append(sub[isub])
+                wts.append(w[isub])
+                dds.append(dd[isub])
+    if first is None or not data:
+        raise RuntimeError("add_archives: no usable archive in %s" % (metafile,))
+    X = torch.stack(data)  # [nunit, npol, nchan, nbin]
+    del data
+    nunit, npol, nchan, nbin = X.shape
+    W = np.stack(wts)
+    nharm = nbin // 2 + 1
+    if palign:
+        phases, _ = palign_phases(eng, X[:, 0], np.stack(dds), W)
+    else:
+        phases = np.zeros(nunit)
+    accum = torch.zeros(npol, nchan, nharm, 2, dtype=torch.float64, device=dev)
+    ph = np.repeat(phases[:, None], nchan, axis=1)
+    for ipol in range(npol):
+        eng.rotate_accumulate(X[:, ipol], ph, W, accum[ipol])
+    tw = torch.as_tensor(W.sum(axis=0), dtype=torch.float64, device=dev)
+    spec = torch.view_as_complex(accum).reshape(npol * nchan, nharm)
+    port = eng.irfft_rows(spec, nbin).reshape(npol, nchan, nbin)
+    good = (tw > 0)[None, :, None]
+    port = torch.where(good, port / torch.where(tw > 0, tw, torch.ones_like(tw))[None, :, None],
+                       torch.zeros_like(port))
+    port = port.cpu().numpy()
+    w01 = np.where(W.sum(axis=0) > 0, 1.0, 0.0)
+    if outfile is not None and dist_info()[0] == 0:
+        meta = _arch.open_archive(first_name, tscrunch=True, pscrunch=pscrunch,
+                                  rm_baseline=rm_baseline).meta
+        meta = {k: v for k, v in meta.items() if k != "subints"}
+        unload_new_archive(port[None], meta, outfile, DM=None, dmc=int(first.dmc),
+                           weights=w01[None], quiet=quiet)
+    return port, phases, w01
+
+
+psradd_archives = add_archives
+
+
+def smooth_archive(archive, outfile=None, smart=True, quiet=False, **kwargs):
+    """A wavelet-smoothed copy of an archive, the package's stand-in for
+    ``psrsmooth -W`` (ppalign.py:40-52): every channel of positive weight, of
+    every subint and polarisation, through Engine.smart_smooth_rows with the
+    levels DataPortrait.smooth_portrait(smart=True) searches (smart=False:
+    wavelet_smooth_rows; kwargs as pplib.smart_smooth / wavelet_smooth take
+    them); rows of weight 0 are written unchanged.  The output is
+    ``<archive>.sm`` (psrsmooth's naming) unless outfile is given, with the
+    archive's own metadata.  This is the package's from-definition db8
+    smoothing: it is not pinned against psrsmooth.
+    Returns the output's name."""
+    from .engine import get_engine
+    from .pplib import smart_smooth_levels, unload_new_archive, _check_wavelet
+    _check_wavelet(kwargs.get("wavelet", "db8"))
+    threshtype = kwargs.get("threshtype", "hard")
+    if threshtype not in ("hard", "soft"):
+        raise ValueError("threshtype %r: 'hard' or 'soft'" % (threshtype,))
+    d = _arch.load_data(archive, dedisperse=False, dededisperse=False, tscrunch=False,
+                        pscrunch=False, rm_baseline=False, quiet=True, host=False)
+    nsub, npol, nchan, nbin = d.nsub, d.npol, d.nchan, d.nbin
+    if nbin % 2:
+        raise ValueError("nlevel=%d: the length of the data, %d, must be a multiple of 2^nlevel"
+                         % (1, nbin))
+    eng = get_engine()
+    sub = torch.as_tensor(d.subints, dtype=torch.float64, device=eng.device).clone()
+    w = np.asarray(d.weights, dtype=np.float64)
+    on = torch.as_tensor(np.repeat((w > 0.0)[:, None, :], npol, axis=1), device=eng.device)
+    rows = sub[on]  # [nrow, nbin]
+    if rows.shape[0]:
+        if smart:
+            L = smart_smooth_levels(nbin, min(8, int(np.log2(nbin))))
+            sm = eng.smart_smooth_rows(rows, L, kwargs.get("rchi2_tol", 0.1), threshtype)[0]
+        else:
+            nlevel = int(kwargs.get("nlevel", 5))
+            if nlevel < 1 or nbin % (1 << nlevel):
+                raise ValueError("nlevel=%d: the length of the data, %d, must be a multiple of "
+                                 "2^nlevel" % (nlevel, nbin))
+            sm = eng.wavelet_smooth_rows(rows, nlevel, float(kwargs.get("fact", 1.0)), threshtype)
+        sub[on] = sm
+    if outfile is None:
+        outfile = str(archive) + ".sm"
+    meta = _arch.open_archive(archive, rm_baseline=False).meta
+    meta = {k: v for k, v in meta.items() if k != "subints"}
+    unload_new_archive(sub, meta, outfile, DM=None, dmc=int(d.dmc), weights=w, quiet=quiet)
+    return outfile
+
+
+psrsmooth_archive = smooth_archive
+
+
+def _first_archive(metafile):
+    files = _datafiles(metafile)
+    if not files:
+        raise RuntimeError("%s names no archive" % (metafile,))
+    return files[0]
+
+
+def run(metafile, initial_guess=None, fwhm=None, fit_dm=True, tscrunch=False, pscrunch=True,
+        SNR_cutoff=0.0, outfile=None, palign=False, norm=None, smooth=False, rot_phase=0.0,
+        place=None, niter=1, quiet=True):
+    """ppalign's command line (ppalign.py:341-380): make the starting template
+    where none is given, align_archives, optionally smooth_archive.
+
+    No initial_guess and no fwhm: add_archives(metafile, palign=palign) into a
+    temporary file.  fwhm: a constant portrait of one Gaussian component of
+    that FWHM at phase 0.5 with the first archive's shape
+    (make_constant_portrait).  A one-channel initial_guess: the first
+    archive's own T-, P- and F-scrunched profile in every channel.  The
+    temporary file (tempfile, in the working directory; rank 0 makes it and
+    the other ranks wait for its name) is removed in every case.  Returns
+    align_archives' portrait."""
+    import os
+    import tempfile
+    from .pplib import make_constant_portrait
+    rank, world = dist_info()
+    tmp = None
+
+    def tmp_name():
+        fd, name = tempfile.mkstemp(prefix="ppalign.", suffix=".tmp.fits", dir=os.getcwd())
+        os.close(fd)
+        return name
+
+    try:
+        make = None
+        if initial_guess is None and fwhm is None:
+            def make(out):
+                add_archives(metafile, out, palign=palign, pscrunch=pscrunch, quiet=quiet)
+        elif fwhm:
+            def make(out):
+                archive = _first_archive(metafile)
+                nbin = _arch.open_archive(archive, rm_baseline=False).meta.nbin
+                make_constant_portrait(archive, out, profile=gaussian_profile(nbin, 0.5, float(fwhm)),
+                                       DM=0.0, dmc=False, weights=None, quiet=quiet)
+        elif _arch.open_archive(initial_guess, rm_baseline=False).meta.nchan == 1:
+            def make(out):
+                make_constant_portrait(_first_archive(metafile), out, profile=None, DM=0.0,
+                                       dmc=False, weights=None, quiet=quiet)
+        if make is not None:
+            if rank == 0:
+                tmp = tmp_name()
+                make(tmp)
+            if world > 1:  # the other ranks wait here for rank 0's file
+                names = [tmp]
+                torch.distributed.broadcast_object_list(names, src=0)
+                initial_guess = names[0]
+            else:
+                initial_guess = tmp
+        aligned = align_archives(metafile, initial_guess=initial_guess, fit_dm=fit_dm,
+                                 tscrunch=tscrunch, pscrunch=pscrunch, SNR_cutoff=SNR_cutoff,
+                                 outfile=outfile, norm=norm, rot_phase=rot_phase, place=place,
+                                 niter=niter, quiet=quiet)
+        if smooth and rank == 0:
+            if outfile is None:
+                outfile = metafile + ".algnd.fits"
+            smooth_archive(outfile, quiet=quiet)
+        return aligned
+    finally:
+        if tmp is not None and os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def _parser():
+    """The reference's option table (ppalign.py:247-312): the same letters,
+    destinations and defaults."""
+    import argparse
+    p = argparse.ArgumentParser(
+        prog="ppalign", usage="%(prog)s -M <metafile> [options]",
+        description="Aligns and averages homogeneous archives by fitting DMs and phases")
+    p.add_argument("-M", "--metafile", default=None, metavar="metafile", dest="metafile",
+                   help="Metafile of archives to average together.")
+    p.add_argument("-I", "--init", default=None, metavar="initial_guess", dest="initial_guess",
+                   help="Archive containing initial alignment guess.  The archives are added "
+                        "(add_archives) if -I is not used.")
+    p.add_argument("-g", "--width", default=None, metavar="fwhm", dest="fwhm",
+                   help="Use a single Gaussian component of given FWHM to align archives.  "
+                        "Overides -I.")
+    p.add_argument("-D", "--no_DM", default=True, action="store_false", dest="fit_dm",
+                   help="Align the subintegrations/archives with a fit for phase only.")
+    p.add_argument("-T", "--tscr", default=False, action="store_true", dest="tscrunch",
+                   help="Tscrunch archives for the iterations.")
+    p.add_argument("-p", "--poln", default=True, action="store_false", dest="pscrunch",
+                   help="Output average Stokes portraits, not just total intensity.")
+    p.add_argument("-C", "--cutoff", default=0.0, metavar="SNR_cutoff", dest="SNR_cutoff",
+                   help="S/N ratio cutoff to apply to input archives. [default=0.0]")
+    p.add_argument("-o", "--outfile", default=None, metavar="outfile", dest="outfile",
+                   help="Name of averaged output archive. [default=metafile.algnd.fits]")
+    p.add_argument("-P", "--palign", default=False, action="store_true", dest="palign",
+                   help="Phase-align the archives that are added if -I is not used. "
+                        "[default=False]")
+    p.add_argument("-N", "--norm", default=None, metavar="normalization", dest="norm",
+                   help="Normalize the final averaged data by channel ('None' [default], 'mean', "
+                        "'max' (not recommended), 'prof', 'rms', or 'abs').")
+    p.add_argument("-s", "--smooth", default=False, action="store_true", dest="smooth",
+                   help="Output a second averaged archive, wavelet-smoothed (smooth_archive). "
+                        "[default=False]")
+    p.add_argument("-r", "--rot", default=0.0, metavar="phase", dest="rot_phase",
+                   help="Additional rotation to add to averaged archive. [default=0.0]")
+    p.add_argument("--place", default=None, metavar="place", dest="place",
+                   help="Roughly place pulse to be at the phase given.  Overrides --rot. "
+                        "[default=None]")
+    p.add_argument("--niter", default=1, metavar="int", dest="niter",
+                   help="Number of iterations to complete. [default=1]")
+    p.add_argument("--verbose", default=True, action="store_false", dest="quiet",
+                   help="More to stdout.")
+    return p
+
+
+def main(argv=None):
+    """python -m pulseportraiture_amd.ppalign -M <metafile> [options]."""
+    parser = _parser()
+    o = parser.parse_args(argv)
+    if o.metafile is None or not int(o.niter):
+        parser.print_help()
+        return 0
+    rot_phase, place = np.float64(o.rot_phase), None
+    if o.place is not None:
+        rot_phase, place = 0.0, np.float64(o.place)
+    run(o.metafile, initial_guess=o.initial_guess, fwhm=o.fwhm, fit_dm=o.fit_dm,
+        tscrunch=o.tscrunch, pscrunch=o.pscrunch, SNR_cutoff=float(o.SNR_cutoff),
+        outfile=o.outfile, palign=o.palign, norm=o.norm, smooth=o.smooth, rot_phase=rot_phase,
+        place=place, niter=int(o.niter), quiet=o.quiet)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -1327,6 +1327,50 @@ def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None, quiet=
         print("\nUnloaded %s.\n" % outfile)
 
 
+def scrunched_profile(bunch):
+    """The T-, P- and F-scrunched profile [nbin] of a load_data bunch loaded as
+    stored (pscrunch=True; subints on the host or the device): per subint the
+    dedispersed, weighted sum over channels (Engine.rotate_fscrunch with the
+    rotation load_data(dedisperse=True) applies, none when the archive is
+    stored dedispersed, and the archive's weights), the subints added and
+    divided by the sum of every weight -- arch.tscrunch() then arch.fscrunch()
+    with PSRCHIVE's weighted means.  Zeros when no weight is positive."""
+    from .archive import stored_dedispersion_phases
+    w = np.asarray(bunch.weights, dtype=np.float64)
+    profs = _engine().rotate_fscrunch(bunch.subints[:, 0], stored_dedispersion_phases(bunch), w)
+    wsum = w.sum()
+    prof = profs.sum(dim=0).cpu().numpy()
+    return prof / wsum if wsum > 0.0 else np.zeros_like(prof)
+
+
+def make_constant_portrait(archive, outfile, profile=None, DM=0.0, dmc=False, weights=None,
+                           quiet=False):
+    """Fill an archive with one profile, pplib.py:958-994 without PSRCHIVE:
+    outfile gets the nsub, npol, nchan, nbin, frequencies, epochs, etc. of
+    archive (an archive load_data reads) and profile [nbin] in every (subint,
+    polarisation, channel), stored with header DM ``DM`` in the state ``dmc``
+    says, with ``weights`` [nsub, nchan] (ones when None), through
+    unload_new_archive.  profile=None: the archive's own T-, P- and F-scrunched
+    profile (scrunched_profile).  A profile whose length is not the archive's
+    nbin is a ValueError (an assertion in the reference)."""
+    from . import archive as _archive
+    meta = _archive.open_archive(archive, rm_baseline=False).meta
+    if profile is None:
+        profile = scrunched_profile(_archive.load_data(
+            archive, dedisperse=False, tscrunch=False, pscrunch=True, rm_baseline=False,
+            quiet=True, host=False))
+    profile = np.asarray(profile, dtype=np.float64)
+    nsub, npol, nchan, nbin = meta.nsub, meta.npol, meta.nchan, meta.nbin
+    if profile.ndim != 1 or len(profile) != nbin:
+        raise ValueError("len(profile) != number of bins in dummy archive (%s, %d)" % (
+            profile.shape, nbin))
+    if weights is None:
+        weights = np.ones([nsub, nchan])
+    data = np.empty([nsub, npol, nchan, nbin])
+    data[...] = profile
+    unload_new_archive(data, meta, outfile, DM=DM, dmc=dmc, weights=weights, quiet=quiet)
+
+
 def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.fits", nsub=1, npol=1, nchan=512,
                      nbin=2048, nu0=1500.0, bw=800.0, tsub=300.0, phase=0.0, dDM=0.0,
                      start_MJD=None, weights=None, noise_stds=1.0, scales=1.0, dedispersed=False,
