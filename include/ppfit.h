@@ -35,6 +35,7 @@
  *   ppf_resid_chi2_rows     <- pplib.get_red_chi2 per channel in
  *                              GetTOAs.get_channels_to_zap  pptoas.py:1201-1278
  *   ppf_pca_portraits       <- pplib.pca                       pplib.py:1497-1534
+ *   ppf_pca_gram_portraits  <- pplib.pca, more channels than bins (np.cov + eigh)
  *                              (as ppspline.make_spline_model calls it,
  *                              ppspline.py:67-82, batched over portraits)
  *   ppf_gauss_fit_batch     <- pplib.fit_gaussian_portrait     pplib.py:1924-2052
@@ -199,6 +200,10 @@ int ppf_set_trace(ppf_ctx* ctx, double* buf, int32_t cap);
 int ppf_get_kernel_time(ppf_ctx* ctx, int kernel_id, double* total_ms,
                         int64_t* launches);
 int ppf_reset_kernel_times(ppf_ctx* ctx);
+/* ms[5]: the PPF_K_PCA time of ppf_pca_gram_portraits calls made under
+ * ppf_set_timing since the last reset, split into the mean pass, the Gram
+ * tiles, the sum over slabs (with the trace), the Jacobi on G and the emit. */
+int ppf_get_pca_gram_times(ppf_ctx* ctx, double* ms);
 /* Device self-test of the cross-lane primitives the kernels rely on
  * (DPP row/quad moves, permlane16/32 swaps, readlane).  fails[t] (t <
  * PPF_SELFTEST_N) = number of lanes where test t is wrong; all 0 = pass.   */
@@ -366,10 +371,35 @@ int ppf_pca_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
                       double* eigvec /* [nport][ncomp][nbin]: vectors as rows */,
                       int32_t* info /* [nport][2] */);
 
+/* The same principal components from the nbin x nbin covariance itself, as
+ * the reference forms it (np.cov, then eigh): for portraits with more
+ * channels than bins, where the rows of A outnumber its rank.  G = A^T A is
+ * summed on the fp64 matrix cores (ppfit_gram.hip) without storing A: 64 x
+ * 64 tiles of the lower triangle, the channels in slabs of 256 whose partial
+ * tiles meet in a second launch in slab order, the upper triangle a copy.
+ * The Jacobi of ppf_pca_portraits then runs on G's nbin rows; the norms of
+ * the rotated rows are the eigenvalues.  Rows of norm at most
+ * nchan eps trace(G), the bound on |G - exact|_F, are null beside the rows
+ * entry's own floor.  mean_prof is bitwise ppf_pca_portraits'; eigenvalues
+ * and vectors agree with it to rounding, not bitwise.  Sign, order, info,
+ * the weights' rules and the reproducibility contract are the sister
+ * entry's.
+ *   2 <= nchan <= PPF_MAX_NCHAN, 16 <= nbin <= 2048 (PPF_ERR_UNSUPPORTED
+ * above either limit), 1 <= ncomp <= min(nchan, nbin).  G and the partial
+ * tiles are workspace (ppf_set_workspace_limit splits the call over
+ * portraits).                                                              */
+int ppf_pca_gram_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                           const double* port /* [nport][nchan][nbin] */,
+                           const double* weights /* [nport][nchan] */, int32_t ncomp,
+                           double* mean_prof /* [nport][nbin] */,
+                           double* eigval /* [nport][ncomp] */,
+                           double* eigvec /* [nport][ncomp][nbin]: vectors as rows */,
+                           int32_t* info /* [nport][2] */);
+
 /* proj[p][n][e] = (port[p][n] - mean_prof[p]) . eigvec[p][e] and, when
  * reconst is not NULL, reconst[p][n] = sum_e proj[p][n][e] eigvec[p][e] +
- * mean_prof[p] (reconstruct_portrait, pplib.py:1536-1553).  nchan <= 2048,
- * 1 <= ncomp <= min(2048, nbin); proj [nport][nchan][ncomp], reconst
+ * mean_prof[p] (reconstruct_portrait, pplib.py:1536-1553).  nchan <=
+ * PPF_MAX_NCHAN, 1 <= ncomp <= min(2048, nbin); proj [nport][nchan][ncomp], reconst
  * [nport][nchan][nbin].                                                    */
 int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
                     const double* mean_prof, int32_t ncomp, const double* eigvec, double* proj,

@@ -134,6 +134,9 @@ EXPORTS = {
                          ctypes.c_double, _dp], ctypes.c_int),
     "ppf_pca_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                            ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_pca_gram_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_get_pca_gram_times": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     "ppf_pca_project": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                          ctypes.c_int32, _dp, _dp, _dp], ctypes.c_int),
     "ppf_wavelet_smooth_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,

@@ -79,6 +79,8 @@ struct ppf_ctx {
   int opt[PPF_NUM_OPTS] = {1, 1, 512, 1, 1, 0};
   double ktime[PPF_NUM_KERNELS] = {0};
   int64_t klaunch[PPF_NUM_KERNELS] = {0};
+  // ppf_pca_gram_portraits under timing: mean pass, Gram tiles, slab sum, Jacobi, emit
+  double gram_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 namespace {
@@ -887,6 +889,13 @@ int ppf_reset_kernel_times(ppf_ctx* ctx) {
   if (!ctx) return PPF_ERR_INVALID;
   if (int r = resolve_timing(ctx)) return r;
   for (int i = 0; i < PPF_NUM_KERNELS; ++i) { ctx->ktime[i] = 0.0; ctx->klaunch[i] = 0; }
+  for (double& v : ctx->gram_ms) v = 0.0;
+  return PPF_OK;
+}
+
+int ppf_get_pca_gram_times(ppf_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return PPF_ERR_INVALID;
+  for (int i = 0; i < 5; ++i) ms[i] = ctx->gram_ms[i];
   return PPF_OK;
 }
 
@@ -1806,6 +1815,143 @@ int ppf_pca_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, 
   return PPF_OK;
 }
 
+int ppf_pca_gram_portraits(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                           const double* port, const double* weights, int32_t ncomp,
+                           double* mean_prof, double* eigval, double* eigvec, int32_t* info) {
+  if (!ctx || !port || !weights || !mean_prof || !eigval || !eigvec || !info)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nport <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  if (nbin > kPcaMaxRows)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: the covariance has at most %d rows", nbin,
+                kPcaMaxRows);
+  if (nchan < 2) return fail(ctx, PPF_ERR_INVALID, "nchan=%d: a PCA needs at least 2 rows", nchan);
+  if (nchan > PPF_MAX_NCHAN)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: at most %d channels per portrait", nchan,
+                PPF_MAX_NCHAN);
+  if (ncomp < 1 || ncomp > std::min(nchan, nbin))
+    return fail(ctx, PPF_ERR_INVALID, "ncomp=%d: 1..min(nchan, nbin)=%d", ncomp,
+                std::min(nchan, nbin));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the weights are checked on the host, as ppf_pca_portraits checks them
+  std::vector<double> hw((size_t)nport * nchan);
+  HIPCHK(ctx, hipMemcpyAsync(hw.data(), weights, hw.size() * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int p = 0; p < nport; ++p) {
+    int npos = 0;
+    for (int n = 0; n < nchan; ++n) {
+      const double w = hw[(size_t)p * nchan + n];
+      if (!std::isfinite(w) || w < 0.0)
+        return fail(ctx, PPF_ERR_INVALID, "portrait %d: weight %d is %g (need finite, >= 0)", p, n,
+                    w);
+      npos += w > 0.0;
+    }
+    if (npos < 2)
+      return fail(ctx, PPF_ERR_INVALID, "portrait %d: %d positive weights (need at least 2)", p,
+                  npos);
+  }
+  // per portrait: G [nbin][nbin], the slabs' partial tiles, the row scales
+  // [nchan], |row|^2 [nbin], trace(G), the state, the order [ncomp]
+  const int m = nbin, M = (m + 1) & ~1;
+  const int npair = gram_npair(nbin), nslab = gram_nslab(nchan);
+  const size_t bG = (size_t)m * nbin * sizeof(double), bN = (size_t)m * sizeof(double);
+  const size_t bP = (size_t)nslab * npair * kGramTile * kGramTile * sizeof(double);
+  const size_t bC = (size_t)nchan * sizeof(double), bO = (size_t)ncomp * sizeof(int);
+  const size_t per_port = bG + bP + bC + bN + sizeof(double) + sizeof(PcaState) + bO;
+  // portraits per pass: under the workspace limit and the grid's z extent
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>({(int64_t)nport, ctx->ws_limit / (int64_t)(per_port + 2048), 65535}));
+  const size_t oP = align256((size_t)chunk * bG), oC = align256(oP + (size_t)chunk * bP);
+  const size_t oN = align256(oC + (size_t)chunk * bC), oT = align256(oN + (size_t)chunk * bN);
+  const size_t oS = align256(oT + (size_t)chunk * sizeof(double));
+  const size_t oO = align256(oS + (size_t)chunk * sizeof(PcaState));
+  if (int r = ensure(ctx, ctx->buf[kWs], oO + (size_t)chunk * bO)) return r;
+  char* base = static_cast<char*>(ctx->buf[kWs].p);
+  double* G = reinterpret_cast<double*>(base);
+  double* part = reinterpret_cast<double*>(base + oP);
+  double* scale = reinterpret_cast<double*>(base + oC);
+  double* norm2 = reinterpret_cast<double*>(base + oN);
+  double* trace = reinterpret_cast<double*>(base + oT);
+  PcaState* state = reinterpret_cast<PcaState*>(base + oS);
+  int* order = reinterpret_cast<int*>(base + oO);
+  std::vector<PcaState> hs((size_t)chunk);
+  // under timing, the device time of the launches since the last mark goes to phase i
+  double seen = 0.0;
+  auto mark = [&](int i) -> int {
+    if (!ctx->timing) return PPF_OK;
+    if (int r = resolve_timing(ctx)) return r;
+    if (i >= 0) ctx->gram_ms[i] += ctx->ktime[PPF_K_PCA] - seen;
+    seen = ctx->ktime[PPF_K_PCA];
+    return PPF_OK;
+  };
+  if (int r = mark(-1)) return r;
+  for (int64_t p0 = 0; p0 < nport; p0 += chunk) {
+    const int np = (int)std::min<int64_t>(chunk, nport - p0);
+    const double* x = port + (size_t)p0 * nchan * nbin;
+    double* mean = mean_prof + (size_t)p0 * nbin;
+    HIPCHK(ctx, hipMemsetAsync(state, 0, (size_t)np * sizeof(PcaState), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(order, 0, (size_t)np * bO, ctx->stream));
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_gram_mean, dim3((nbin + 63) / 64, np), dim3(64), 0, ctx->stream, x,
+                             weights + (size_t)p0 * nchan, nchan, nbin, mean, scale);
+        }))
+      return r;
+    if (int r = mark(0)) return r;
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_gram_tiles, dim3(gram_nsuper(nbin), nslab, np), dim3(kBlock), 0,
+                             ctx->stream, x, scale, mean, nchan, nbin, npair, part);
+        }))
+      return r;
+    if (int r = mark(1)) return r;
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_gram_reduce, dim3(npair, kGramTile / 4, np), dim3(kBlock), 0,
+                             ctx->stream, part, nbin, nslab, G);
+          hipLaunchKernelGGL(k_gram_trace, dim3(np), dim3(kBlock), 0, ctx->stream, G, nbin, trace);
+        }))
+      return r;
+    if (int r = mark(2)) return r;
+    // the Jacobi of ppf_pca_portraits on G's rows, with G's own null threshold
+    for (int sweep = 0; sweep <= kPcaMaxSweeps; ++sweep) {
+      if (int r = timed(ctx, PPF_K_PCA, [&] {
+            hipLaunchKernelGGL(k_pca_norms, dim3(m, np), dim3(kBlock), 0, ctx->stream, G, m, nbin,
+                               norm2);
+            hipLaunchKernelGGL(k_pca_sweep, dim3(np), dim3(kBlock), 0, ctx->stream, state, norm2,
+                               m, nbin, sweep, kPcaMaxSweeps);
+            hipLaunchKernelGGL(k_gram_null, dim3((np + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                               ctx->stream, state, trace, nchan, np);
+          }))
+        return r;
+      HIPCHK(ctx, hipMemcpyAsync(hs.data(), state, (size_t)np * sizeof(PcaState),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      bool all_done = true;
+      for (int p = 0; p < np; ++p) all_done = all_done && hs[p].done != 0;
+      if (all_done) break;
+      if (int r = timed(ctx, PPF_K_PCA, [&] {
+            for (int round = 0; round < M - 1; ++round)
+              hipLaunchKernelGGL(k_pca_step, dim3(M / 2, np), dim3(kBlock), 0, ctx->stream, G,
+                                 state, m, M, nbin, round);
+          }))
+        return r;
+    }
+    if (int r = mark(3)) return r;
+    if (int r = timed(ctx, PPF_K_PCA, [&] {
+          hipLaunchKernelGGL(k_pca_rank, dim3(np), dim3(kBlock), bN, ctx->stream, norm2, m, ncomp,
+                             order);
+          hipLaunchKernelGGL(k_pca_emit, dim3(ncomp, np), dim3(kBlock), 0, ctx->stream, G, norm2,
+                             order, state, m, nbin, ncomp, eigval + (size_t)p0 * ncomp,
+                             eigvec + (size_t)p0 * ncomp * nbin, info + (size_t)p0 * 2);
+          hipLaunchKernelGGL(k_gram_sqrt, dim3((np * ncomp + kBlock - 1) / kBlock), dim3(kBlock),
+                             0, ctx->stream, eigval + (size_t)p0 * ncomp, np * ncomp);
+        }))
+      return r;
+    if (int r = mark(4)) return r;
+  }
+  return PPF_OK;
+}
+
 int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, const double* port,
                     const double* mean_prof, int32_t ncomp, const double* eigvec, double* proj,
                     double* reconst) {
@@ -1815,9 +1961,9 @@ int ppf_pca_project(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t nbin, co
   int logN;
   if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
   if (nchan < 1) return fail(ctx, PPF_ERR_INVALID, "nchan=%d", nchan);
-  if (nchan > kPcaMaxRows)
-    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: at most %d rows per portrait", nchan,
-                kPcaMaxRows);
+  if (nchan > PPF_MAX_NCHAN)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d: at most %d channels per portrait", nchan,
+                PPF_MAX_NCHAN);
   if (ncomp < 1 || ncomp > std::min<int>(kPcaMaxRows, nbin))
     return fail(ctx, PPF_ERR_INVALID, "ncomp=%d: 1..%d", ncomp, std::min<int>(kPcaMaxRows, nbin));
   HIPCHK(ctx, hipSetDevice(ctx->device));

@@ -316,6 +316,14 @@ class Engine:
         self._chk(self.lib.ppf_selftest(self.ctx, fails))
         return list(fails)
 
+    def pca_gram_times(self):
+        """Device ms of the Gram-path PCA calls made under set_timing since
+        the last reset: (mean pass, Gram tiles, sum over slabs, Jacobi on G,
+        emit)."""
+        ms = (ctypes.c_double * 5)()
+        self._chk(self.lib.ppf_get_pca_gram_times(self.ctx, ms))
+        return tuple(ms)
+
     def reset_kernel_times(self):
         self._chk(self.lib.ppf_reset_kernel_times(self.ctx))
 
@@ -613,13 +621,21 @@ class Engine:
         out._keep = (f, mean, evd)
         return out.reshape(shape + (nb,))
 
-    def pca_portraits(self, port, weights, ncomp=None):
+    PCA_MAX_ROWS = 2048  # kPcaMaxRows: the rows path's limit on nchan
+
+    def pca_portraits(self, port, weights, ncomp=None, method=None):
         """pplib.pca (pplib.py:1497-1534) of portraits [..., nchan, nbin] with
-        weights [..., nchan] in one call (ppf_pca_portraits): the weighted
-        mean profile [..., nbin], the ncomp (default min(nchan, nbin)) leading
+        weights [..., nchan] in one call: the weighted mean profile
+        [..., nbin], the ncomp (default min(nchan, nbin)) leading
         eigenvalues [..., ncomp] and eigenvectors as rows [..., ncomp, nbin]
         of the weighted covariance, and info [..., 2] (sweeps, converged).
+        method "rows" is the Jacobi on the portrait's rows (ppf_pca_portraits,
+        at most 2,048 channels), "gram" the Jacobi on the nbin x nbin
+        covariance (ppf_pca_gram_portraits, at most 2,048 bins); None takes
+        "rows" up to 2,048 channels and "gram" above.
         Device tensors in, device tensors out."""
+        if method not in (None, "rows", "gram"):
+            raise ValueError("method %r: None, 'rows' or 'gram'" % (method,))
         dev = self.device
         x = _dev_f64(port, dev)
         lead = tuple(x.shape[:-2])
@@ -633,8 +649,11 @@ class Engine:
         eigval = torch.empty((nport, shp), dtype=torch.float64, device=dev)
         eigvec = torch.empty((nport, shp, nbin), dtype=torch.float64, device=dev)
         info = torch.zeros((nport, 2), dtype=torch.int32, device=dev)
-        self._chk(self.lib.ppf_pca_portraits(self.ctx, nport, nchan, nbin, _ptr(x), _ptr(w), nc,
-                                             _ptr(mean), _ptr(eigval), _ptr(eigvec), _ptr(info)))
+        if method is None:
+            method = "rows" if nchan <= self.PCA_MAX_ROWS else "gram"
+        entry = self.lib.ppf_pca_portraits if method == "rows" else self.lib.ppf_pca_gram_portraits
+        self._chk(entry(self.ctx, nport, nchan, nbin, _ptr(x), _ptr(w), nc, _ptr(mean),
+                        _ptr(eigval), _ptr(eigvec), _ptr(info)))
         mean._keep = (x, w)
         return (mean.reshape(lead + (nbin,)), eigval.reshape(lead + (shp,)),
                 eigvec.reshape(lead + (shp, nbin)), info.reshape(lead + (2,)))

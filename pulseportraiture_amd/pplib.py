@@ -880,10 +880,13 @@ def normalize_portrait(port, method="rms", weights=None, return_norms=False,
 # ---------------------------------------------------------------------------
 # PCA of a portrait and the choice of eigenvectors (ppspline model building)
 # ---------------------------------------------------------------------------
-def pca(port, mean_prof=None, weights=None, quiet=False, ncomp=None):
+def pca(port, mean_prof=None, weights=None, quiet=False, ncomp=None, method=None):
     """Principal components of an nchan x nbin portrait, pplib.py:1497-1534,
-    on the device (ppf_pca_portraits: a one-sided Jacobi on the centred,
-    weighted rows; no nbin x nbin covariance is formed).
+    on the device.  method "rows" (ppf_pca_portraits) is a one-sided Jacobi
+    on the centred, weighted rows, with no nbin x nbin covariance formed;
+    "gram" (ppf_pca_gram_portraits) forms the covariance on the fp64 matrix
+    cores and runs the Jacobi on it; None takes "rows" up to 2,048 channels
+    and "gram" above (Engine.pca_portraits).
 
     Returns eigval [r] (descending) and eigvec [nbin, r] (column vectors),
     r = ncomp or min(nchan, nbin): the reference's remaining nbin - r columns
@@ -901,7 +904,7 @@ def pca(port, mean_prof=None, weights=None, quiet=False, ncomp=None):
     if weights is None:
         weights = np.ones(nmes)
     _, eigval, eigvec, _ = _engine().pca_portraits(port, np.asarray(weights, dtype=np.float64),
-                                                   ncomp)
+                                                   ncomp, method)
     return eigval.cpu().numpy(), np.ascontiguousarray(eigvec.cpu().numpy().T)
 
 

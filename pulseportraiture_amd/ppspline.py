@@ -3,7 +3,8 @@
 For an nchan x nbin portrait of aligned profiles (ppalign's output) the model
 is a B-spline representation of the curve the nchan profiles trace in the
 space of a few eigenprofiles (ppspline.py:1-20).  The PCA runs on the device
-(ppf_pca_portraits, batched over portraits), as do the projections
+(ppf_pca_portraits, batched over portraits; ppf_pca_gram_portraits above
+2,048 unzapped channels), as do the projections
 (ppf_pca_project) and the model portraits (ppf_spline_portraits); the curve
 fit is one scipy.interpolate.splprep call per model on nchan x <= 10 numbers
 (FITPACK, third-party to the reference too).
