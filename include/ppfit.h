@@ -24,6 +24,8 @@
  *                              aligns on (ppalign.py:21-38)
  *   ppf_irfft_rows          <- numpy.fft.irfft (final step of ppalign.py:210-213)
  *   ppf_noise_rows          <- pplib.get_noise_PS(chans=True)  pplib.py:2227-2253
+ *   ppf_noise_fit_rows      <- pplib.get_noise_fit(chans=True) pplib.py:2255-2287
+ *   ppf_find_kc_rows        <- pplib.find_kc                   pplib.py:1465-1495
  *   ppf_unpack_subints      <- PSRCHIVE Archive_load + pscrunch in
  *                              pplib.load_data  pplib.py:2670-2732 (with
  *                              include/ppfits.h, the host PSRFITS reader)
@@ -708,6 +710,40 @@ int ppf_irfft_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* spec,
 /* out[r] = get_noise_PS(in[r]) (frac=4)                                   */
 int ppf_noise_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,
                    double* out);
+
+/* out[r] = get_noise_PS(in[r], frac) for any frac > 1 (pplib.py:2227-2253):
+ * the root of the mean power above harmonic int((1 - 1/frac) (nbin/2 + 1)).
+ * ppf_noise_rows is its frac = 4 case.                                     */
+int ppf_noise_rows_frac(ppf_ctx* ctx, int32_t nrow, int32_t nbin, double frac,
+                        const double* in, double* out);
+
+/* noise_out[r] = get_noise_fit(in[r], fact) (pplib.py:2255-2287): with
+ * pows_k = |rfft(in[r])_k|^2 / nbin, k < NH = nbin/2 + 1, and kc = find_kc(pows)
+ * as ppf_find_kc_rows (exp_dc, no weights) finds it,
+ *   k_crit = fact kc;  if k_crit >= NH: k_crit = min(int(0.99 NH), k_crit)
+ *   noise  = sqrt(mean(pows[int(k_crit):]))
+ * kc_out [nrow] and idx_out [nrow] (either may be NULL) receive kc and the
+ * flat index of the winning grid point.  fact > 0; nbin in [16, 8192].  A
+ * row's outputs are bitwise the same whatever else shares the call.  Timed
+ * under PPF_K_NOISE, like ppf_find_kc_rows.                                */
+int ppf_noise_fit_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,
+                       double fact, double* noise_out, int32_t* kc_out, int32_t* idx_out);
+
+/* find_kc (pplib.py:1465-1495) on power spectra pows [nrow][n], 4 <= n <= 8193:
+ * scipy.optimize.brute(Ns = 20, finish = None) of
+ *   sum_k w_k (log10 pows_k - b f_a(k) - dc)^2,  w_k = 1 / errs_k^2 (errs [n],
+ *   shared by the rows; NULL = 1)
+ * over a_i = i (a_hi - a_lo) / 19 + a_lo, b_i = i (max d - min d) / 19,
+ * dc_i = min d + i (max d - min d) / 19, d = log10 pows, i < 20:
+ *   fn 0 (exp_dc):   f_a(k) = e^{-a k}, a in [1/n, 1];
+ *                    kc = the first k with e^{-a k} < 0.005, or n - 1
+ *   fn 1 (half_tri): f_a(k) = max(0, 1 - k / floor(a)), a in [1, n]; kc = floor(a)
+ * idx_out (or NULL) = (ia 20 + ib) 20 + idc of the smallest value; among equal
+ * values the lowest index, and the first NaN before any number, as
+ * numpy.argmin: a row holding a zero, negative or non-finite power, or a
+ * weight that is not finite, returns index 0.                              */
+int ppf_find_kc_rows(ppf_ctx* ctx, int32_t nrow, int32_t n, const double* pows,
+                     const double* errs, int32_t fn, int32_t* kc_out, int32_t* idx_out);
 
 /* data[s][n] = irfft(rfft(model[n]) * e^{2 pi i k phase[s][n]})
  *              + sigma * N(0,1)[Philox4x32-10(seed; bin pair, n, s + sub0)] */

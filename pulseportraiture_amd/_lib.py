@@ -108,6 +108,12 @@ EXPORTS = {
                        ctypes.c_int),
     "ppf_noise_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp],
                        ctypes.c_int),
+    "ppf_noise_rows_frac": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                             _dp, _dp], ctypes.c_int),
+    "ppf_noise_fit_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp,
+                            ctypes.c_double, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_find_kc_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
+                          ctypes.c_int32, _dp, _dp], ctypes.c_int),
     "ppf_resid_chi2_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp,
                              _dp, _dp, _dp, _dp, ctypes.c_double, _dp], ctypes.c_int),
     "ppf_unpack_subints": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -24,7 +24,7 @@ import os
 import numpy as np
 
 from .mjd import MJD, epoch_parts
-from .pplib import DataBunch, Dconst, get_bin_centers
+from .pplib import DataBunch, Dconst, _noise_rows, get_bin_centers
 
 _registry = {}
 
@@ -563,7 +563,7 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
     if b.get("noise_stds") is None and a.eager_noise:
         from .engine import get_engine
         n, npol, nchan, nbin = tuple(sub.shape)
-        b.noise_stds = get_engine().noise_rows(sub.reshape(-1, nbin)).reshape(
+        b.noise_stds = _noise_rows(get_engine(), sub.reshape(-1, nbin)).reshape(
             n, npol, nchan).cpu().numpy()
     if b.get("snr_deferred"):
         if get_SNRs:

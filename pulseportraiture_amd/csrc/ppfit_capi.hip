@@ -1315,21 +1315,69 @@ int ppf_irfft_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* spec,
   });
 }
 
-int ppf_noise_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in, double* out) {
+int ppf_noise_rows_frac(ppf_ctx* ctx, int32_t nrow, int32_t nbin, double frac, const double* in,
+                        double* out) {
   if (!ctx || !in || !out) return fail(ctx, PPF_ERR_INVALID, "null argument");
   if (nrow <= 0) return PPF_OK;
   int logN;
   if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  if (!(frac > 1.0) || !std::isfinite(frac))
+    return fail(ctx, PPF_ERR_INVALID, "frac=%g: must be > 1 and finite", frac);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
-  const int kc = noise_kc(nbin);
+  // pplib.py:2245, kc = int((1 - frac**-1) * len(pows)); frac = 4 is noise_kc
+  const int kc = (int)((1.0 - 1.0 / frac) * (double)(nbin / 2 + 1));
   return timed(ctx, PPF_K_NOISE, [&] {
     if (logN < 0)
       hipLaunchKernelGGL(k_noise_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin),
                          ctx->stream, in, out, kc, tw, nbin);
     LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_rows<LG>, dim3(nrow), dim3(kBlock), 0,
                                          ctx->stream, in, out, kc, tw));
+  });
+}
+
+int ppf_noise_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in, double* out) {
+  return ppf_noise_rows_frac(ctx, nrow, nbin, 4.0, in, out);
+}
+
+int ppf_noise_fit_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in, double fact,
+                       double* noise_out, int32_t* kc_out, int32_t* idx_out) {
+  if (!ctx || !in || !noise_out) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nrow <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  if (!(fact > 0.0) || !std::isfinite(fact))
+    return fail(ctx, PPF_ERR_INVALID, "fact=%g: must be positive and finite", fact);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  return timed(ctx, PPF_K_NOISE, [&] {
+    if (logN < 0)
+      hipLaunchKernelGGL(k_noise_fit_rows_gen, dim3(nrow), dim3(kBlock),
+                         (size_t)(nbin + 2) * sizeof(double), ctx->stream, in, fact, noise_out,
+                         kc_out, idx_out, tw, nbin);
+    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_fit_rows<LG>, dim3(nrow), dim3(kBlock), 0,
+                                         ctx->stream, in, fact, noise_out, kc_out, idx_out, tw));
+  });
+}
+
+int ppf_find_kc_rows(ppf_ctx* ctx, int32_t nrow, int32_t n, const double* pows,
+                     const double* errs, int32_t fn, int32_t* kc_out, int32_t* idx_out) {
+  if (!ctx || !pows || !kc_out) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nrow <= 0) return PPF_OK;
+  if (n < 4 || n > 8193)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "n=%d: outside [4, 8193]", n);
+  if (fn != 0 && fn != 1) return fail(ctx, PPF_ERR_INVALID, "fn=%d: 0 (exp_dc) or 1 (half_tri)", fn);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t lds = (size_t)n * sizeof(double);
+  return timed(ctx, PPF_K_NOISE, [&] {
+    if (fn == 0)
+      hipLaunchKernelGGL(k_find_kc_rows<0>, dim3(nrow), dim3(kBlock), lds, ctx->stream, pows, errs,
+                         n, kc_out, idx_out);
+    else
+      hipLaunchKernelGGL(k_find_kc_rows<1>, dim3(nrow), dim3(kBlock), lds, ctx->stream, pows, errs,
+                         n, kc_out, idx_out);
   });
 }
 

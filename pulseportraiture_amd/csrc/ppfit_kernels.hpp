@@ -849,6 +849,15 @@ __global__ void k_noise_rows_gen(const double* in, double* out, int kc, const do
 __global__ void k_rot_accum_gen(const double* data, const double* phase, const double* weight,
                                 double2* partial, int nsub, int nchan, int nsplit,
                                 const double2* tw, int nbin);
+// get_noise_fit / find_kc (ppfit_noisefit.hip)
+template <int LOGN>
+__global__ void k_noise_fit_rows(const double* in, double fact, double* noise, int* kc_out,
+                                 int* idx_out, const double2* tw);
+__global__ void k_noise_fit_rows_gen(const double* in, double fact, double* noise, int* kc_out,
+                                     int* idx_out, const double2* tw, int nbin);
+template <int FN>
+__global__ void k_find_kc_rows(const double* pows, const double* errs, int n, int* kc_out,
+                               int* idx_out);
 __global__ void k_resid_chi2_gen(ResidArgs a, const double2* tw, int nbin);
 template <bool LTW>
 __global__ void k_dft_rows_mfma(const double* rows, double2* D, int nrows, int nbin, int NHP,

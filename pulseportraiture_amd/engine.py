@@ -1002,14 +1002,61 @@ class Engine:
         out._keep = rows
         return out
 
-    def noise_rows(self, rows):
+    def noise_rows(self, rows, frac=4):
+        """get_noise_PS of each row: the mean of the highest 1/frac of the power
+        spectrum (ppf_noise_rows; ppf_noise_rows_frac for frac != 4)."""
         dev = self.device
         r = _dev_f64(rows, dev)
         r2 = r.reshape(-1, r.shape[-1])
         out = torch.empty(r2.shape[0], dtype=torch.float64, device=dev)
-        self._chk(self.lib.ppf_noise_rows(self.ctx, r2.shape[0], r2.shape[1], _ptr(r2), _ptr(out)))
+        if frac == 4:
+            self._chk(self.lib.ppf_noise_rows(self.ctx, r2.shape[0], r2.shape[1], _ptr(r2),
+                                              _ptr(out)))
+        else:
+            self._chk(self.lib.ppf_noise_rows_frac(self.ctx, r2.shape[0], r2.shape[1],
+                                                   float(frac), _ptr(r2), _ptr(out)))
         out._keep = r2
         return out.reshape(r.shape[:-1])
+
+    def noise_fit_rows(self, rows, fact=1.1, full=False):
+        """get_noise_fit of each row (ppf_noise_fit_rows): the noise from the power
+        above fact * find_kc(power spectrum).  full=True also returns kc and the
+        flat index of the winning grid point (int32 tensors)."""
+        dev = self.device
+        r = _dev_f64(rows, dev)
+        r2 = r.reshape(-1, r.shape[-1])
+        nrow = r2.shape[0]
+        out = torch.empty(nrow, dtype=torch.float64, device=dev)
+        kc = torch.empty(nrow, dtype=torch.int32, device=dev) if full else None
+        idx = torch.empty(nrow, dtype=torch.int32, device=dev) if full else None
+        self._chk(self.lib.ppf_noise_fit_rows(self.ctx, nrow, r2.shape[1], _ptr(r2), float(fact),
+                                              _ptr(out), _ptr(kc), _ptr(idx)))
+        out._keep = r2
+        out = out.reshape(r.shape[:-1])
+        if full:
+            return out, kc.reshape(r.shape[:-1]), idx.reshape(r.shape[:-1])
+        return out
+
+    def find_kc_rows(self, pows, errs=None, fn="exp_dc"):
+        """find_kc of each power spectrum pows [..., n] (ppf_find_kc_rows); errs [n]
+        weights the harmonics by 1 / errs**2 (None: no weights).  Returns kc and
+        the flat index of the winning grid point (int32 tensors)."""
+        if fn not in ("exp_dc", "half_tri"):
+            raise ValueError("find_kc_rows: fn %r is neither 'exp_dc' nor 'half_tri'" % (fn,))
+        dev = self.device
+        p = _dev_f64(pows, dev)
+        p2 = p.reshape(-1, p.shape[-1])
+        nrow, n = p2.shape
+        e = _dev_f64(errs, dev)
+        if e is not None and e.numel() != n:
+            raise ValueError("find_kc_rows: errs has %d elements, the spectra %d"
+                             % (e.numel(), n))
+        kc = torch.empty(nrow, dtype=torch.int32, device=dev)
+        idx = torch.empty(nrow, dtype=torch.int32, device=dev)
+        self._chk(self.lib.ppf_find_kc_rows(self.ctx, nrow, n, _ptr(p2), _ptr(e),
+                                            0 if fn == "exp_dc" else 1, _ptr(kc), _ptr(idx)))
+        kc._keep = (p2, e)
+        return kc.reshape(p.shape[:-1]), idx.reshape(p.shape[:-1])
 
     def resid_chi2_rows(self, data, phase, model, scale, errs, dof, tau=None,
                         model_row=None):
@@ -1212,7 +1259,8 @@ for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portrai
               "gauss_eval_join", "gauss_fit_join",
               "instrumental_response_rows",
               "response_table", "tscrunch",
-              "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "resid_chi2_rows",
+              "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "noise_fit_rows",
+              "find_kc_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "rotate_fscrunch", "spec_cache",
               "rotate_accumulate_spec",
               "synth", "pack_subints", "fake_subints"):

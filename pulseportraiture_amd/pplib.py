@@ -769,21 +769,126 @@ def weighted_mean(data, errs=1.0):
 # ---------------------------------------------------------------------------
 # GPU-backed utilities (libppfit)
 # ---------------------------------------------------------------------------
-def get_noise(data, method=default_noise_method, **kwargs):
-    """pplib.py:2206-2225 (PS method on the GPU)."""
-    if method != "PS":
-        raise NotImplementedError("get_noise method %r: only 'PS' is on the hot path" % method)
-    return get_noise_PS(data, **kwargs)
+def get_noise(data, method=None, **kwargs):
+    """Estimate the off-pulse noise on the GPU, pplib.py:2206-2225: "PS" from
+    the top of the power spectrum (get_noise_PS), "fit" from the power above
+    a fitted noise-floor harmonic (get_noise_fit).  method=None takes
+    default_noise_method as it is at the call."""
+    if method is None:
+        method = default_noise_method
+    if method == "PS":
+        return get_noise_PS(data, **kwargs)
+    elif method == "fit":
+        return get_noise_fit(data, **kwargs)
+    else:
+        print("Unknown get_noise method.")
+        return 0
 
 
 def get_noise_PS(data, frac=4, chans=False):
-    """Noise from the top quarter of the power spectrum, pplib.py:2227-2253."""
-    if frac != 4:
-        raise NotImplementedError("frac != 4")
+    """Noise from the highest 1/frac of the power spectrum, pplib.py:2227-2253."""
     data = np.asarray(data, dtype=np.float64)
     rows = data if chans else data.ravel()[None]
-    out = _engine().noise_rows(rows).cpu().numpy()
+    out = _engine().noise_rows(rows, frac=frac).cpu().numpy()
     return out if chans else float(out[0])
+
+
+def get_noise_fit(data, fact=1.1, chans=False):
+    """Noise from the power above fact * find_kc(power spectrum), the harmonic
+    where a fitted exponential decay meets the noise floor, pplib.py:2255-2287
+    (one workgroup per row, ppf_noise_fit_rows)."""
+    data = np.asarray(data, dtype=np.float64)
+    rows = data if chans else data.ravel()[None]
+    out = _engine().noise_fit_rows(rows, fact=fact).cpu().numpy()
+    return out if chans else float(out[0])
+
+
+# host arrays above this many bytes go through _noise_rows in pieces
+_NOISE_CHUNK_BYTES = 1 << 28
+
+
+def _noise_rows(eng, rows):
+    """Noise of every row (last axis) by default_noise_method, as a device
+    tensor: where the drivers estimate noise_stds and where a fit is asked to
+    estimate its own errs."""
+    if default_noise_method == "PS":
+        fn = eng.noise_rows
+    elif default_noise_method == "fit":
+        fn = eng.noise_fit_rows
+    else:
+        raise ValueError("default_noise_method %r is neither 'PS' nor 'fit'"
+                         % (default_noise_method,))
+    if isinstance(rows, np.ndarray) and rows.ndim > 1 and rows.nbytes > _NOISE_CHUNK_BYTES:
+        import torch
+        per = max(1, _NOISE_CHUNK_BYTES // max(1, rows[0].nbytes))
+        return torch.cat([fn(rows[i:i + per]) for i in range(0, len(rows), per)])
+    return fn(rows)
+
+
+def _fit_errs(eng, data, errs):
+    """The errs (or noise) a fit call is given.  None leaves the estimate to
+    the fit kernels, which is get_noise_PS per profile; under any other
+    default_noise_method it is computed here from the data instead (eng None:
+    the default engine, fetched only then)."""
+    if errs is not None or default_noise_method == "PS":
+        return errs
+    if not hasattr(data, "device"):  # not a tensor
+        data = np.asarray(data, dtype=np.float64)
+    return _noise_rows(eng if eng is not None else _engine(), data)
+
+
+def half_triangle_function(a, b, dc, N):
+    """A half-triangle of base floor(a) and height b on a baseline dc, N long
+    (pplib.py:1436-1446)."""
+    base = int(np.floor(a))
+    out = np.full(int(N), dc, dtype=np.float64)
+    k = np.arange(min(base, int(N)))
+    out[:len(k)] += np.float64(b) - (np.float64(b) / base) * k  # b at k = 0, 0 at k = base
+    return out
+
+
+def find_kc_function(params, data, errs=1.0, fn="exp_dc"):
+    """The (weighted) sum of squares find_kc minimises, pplib.py:1448-1463:
+    params = (a, b, dc) of b exp(-a k) + dc ('exp_dc') or of
+    half_triangle_function ('half_tri') against data."""
+    if fn not in ("exp_dc", "half_tri"):
+        return 0.0
+    a, b, dc = params[:3]
+    n = len(data)
+    model = half_triangle_function(a, b, dc, n) if fn == "half_tri" else \
+        b * np.exp(-a * np.arange(n)) + dc
+    resid = (data - model) / errs
+    return np.sum(resid ** 2.0)
+
+
+def find_kc(pows, errs=1.0, fn="exp_dc"):
+    """The harmonic where the noise floor of the power spectrum pows begins,
+    pplib.py:1465-1495: the 20 x 20 x 20 grid search of find_kc_function over
+    log10(pows) on the device (ppf_find_kc_rows).  errs is a scalar (which
+    changes no minimum) or one value per harmonic.  Returns a Python int; an
+    unknown fn returns 0.
+
+    Extension: a 2-D pows [nspec, n] returns an int array, one device call
+    for all the spectra (errs then applies to each of them)."""
+    if fn not in ("exp_dc", "half_tri"):
+        return 0
+    pows = np.asarray(pows, dtype=np.float64)
+    e = None if np.ndim(errs) == 0 else np.asarray(errs, dtype=np.float64)
+    kc = _engine().find_kc_rows(pows if pows.ndim > 1 else pows[None], errs=e, fn=fn)[0]
+    kc = kc.cpu().numpy()
+    return kc.astype(int) if pows.ndim > 1 else int(kc[0])
+
+
+def get_SNR(prof, fudge=3.25):
+    """An estimate of the profile's signal-to-noise ratio from its equivalent
+    width (Lorimer & Kramer 2005), pplib.py:2289-2308; the baseline is assumed
+    removed."""
+    prof = np.asarray(prof, dtype=np.float64)
+    area = prof.sum()
+    width = area / prof.max()  # equivalent width [bin]
+    if width <= 0.0:           # no pulse above the baseline: S/N 0
+        return np.float64(0.0) / fudge
+    return area / (get_noise(prof) * width ** 0.5) / fudge
 
 
 def _rot_phases(shape, phase, DM, Ps, freqs, nu_ref):
@@ -833,6 +938,7 @@ def rotate_profile(profile, phase=0.0):
 def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100):
     """FFTFIT: brute force + Nelder-Mead on the GPU, pplib.py:2054-2100."""
     t0 = time.time()
+    noise = _fit_errs(None, data, noise)
     out = _engine().phase_shift_batch(np.asarray(data, dtype=np.float64),
                                       np.asarray(model, dtype=np.float64), noise=noise,
                                       Ns=Ns, bounds=bounds).cpu().numpy()[0]

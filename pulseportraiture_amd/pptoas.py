@@ -16,7 +16,8 @@ from . import archive as _arch
 from .engine import FitPipeline, get_engine
 from .mjd import MJD, add_days_parts, epoch_parts
 from .pplib import (DataBunch, F0_fact, phase_transform, gen_gaussian_portraits_device,
-                    guess_fit_freq, scattering_alpha, scattering_times, weighted_mean, write_TOAs)
+                    guess_fit_freq, scattering_alpha, scattering_times, weighted_mean, write_TOAs,
+                    _noise_rows, _fit_errs)
 from .pptoaslib import phase_shifts, report_failure
 from .templates import TemplateSource, chan_bw, row_keys
 from .toas import TOA, TOABlock, TOAList, FlagColumn, MJDArray  # noqa: F401
@@ -707,7 +708,7 @@ class GetTOAs:
         if return_fit:
             ns = data.get("noise_stds")
             noise = ns[isub, 0] if ns is not None else \
-                eng.noise_rows(np.asarray(data.subints)[isub, 0]).cpu().numpy()
+                _noise_rows(eng, np.asarray(data.subints)[isub, 0]).cpu().numpy()
             return port, model_scaled, data.ok_ichans[isub], data.freqs[isub], noise
 
     def get_channels_to_zap(self, SNR_threshold=8.0, rchi2_threshold=1.3, iterate=True,
@@ -727,7 +728,7 @@ class GetTOAs:
             if len(fr.where):
                 noise = fr.noise
                 if np.isnan(noise).any():  # load_data's get_noise on the device
-                    est = eng.noise_rows(fr.rows).cpu().numpy()
+                    est = _noise_rows(eng, fr.rows).cpu().numpy()
                     noise = np.where(np.isnan(noise), est, noise)
                 chi2 = eng.resid_chi2_rows(fr.rows, fr.phase, fr.models, fr.scale, noise,
                                            data.nbin - 2, tau=fr.tau,
@@ -981,13 +982,15 @@ class GetTOAs:
             else:
                 d = sub[rel] if not _arch._is_tensor(sub) else sub[_arch_index(rel, sub)]
             # errs None: the device estimates get_noise_PS per channel, as
-            # load_data's noise_stds (pplib.py:2744-2748); per-channel rows
-            # shared by every subint go as one row
+            # load_data's noise_stds (pplib.py:2744-2748), or _fit_errs does by
+            # another default_noise_method; per-channel rows shared by every
+            # subint go as one row
             pipe.submit((key, g, _take(job.nu_fits_a, s)),
                         d, job.models, job.row("freqs", s), _take(data.Ps, s),
                         _take(job.init, s), list(ffs[g[0]]),
                         nu_fit=_take(job.nu_fits_a, s), nu_out=_take(job.nu_refs_a, s),
-                        errs=None if errs is None else _take(errs, s),
+                        errs=_fit_errs(None, d, None) if errs is None
+                        else _take(errs, s),
                         log10_tau=self.log10_tau, option=0, is_toa=True,
                         chan_mask=job.row("mask", s), weights=job.row("weights", s),
                         model_idx=_take(job.midx, s), guess=True, guess_Ns=100,

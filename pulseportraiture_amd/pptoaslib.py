@@ -11,6 +11,7 @@ import time
 
 import numpy as np
 
+from . import pplib
 from .pplib import (DataBunch, Dconst, RCSTRINGS, scattering_times,
                     scattering_portrait_FT)
 
@@ -102,6 +103,7 @@ def fit_portraits_batch(data, model, init, P, freqs, nu_fits=None, nu_outs=None,
     import torch
     eng = get_engine(device)
     t0 = time.time()
+    errs = pplib._fit_errs(eng, data, errs)
     kw = dict(nu_fit=nu_fits, nu_out=nu_outs, errs=errs, chan_mask=chan_mask, weights=weights,
               model_idx=model_idx, log10_tau=log10_tau, option=option, is_toa=is_toa,
               guess=guess, guess_Ns=guess_Ns, guess_wrap=guess_wrap, guess_nu=guess_nu,
