@@ -11,6 +11,12 @@
  *                              (+ the get_TOAs initial guess pptoas.py:420-456,
  *                               ppalign.py:180-185, batched over subints)
  *   ppf_phase_shift_batch   <- pplib.fit_phase_shift          pplib.py:2054-2100
+ *   ppf_phase_tau_batch     <- pptoaslib.fit_portrait_full on one channel with
+ *                              fit_flags [1,0,0,1,0]: the fit_phase_shift_scat
+ *                              call that GetTOAs.get_narrowband_TOAs leaves
+ *                              commented out (pptoas.py:752-753, 982-988;
+ *                              objective pptoaslib.py:525-643, post-fit
+ *                              pptoaslib.py:645-731)
  *   ppf_rotate_rows         <- pplib.rotate_data / rotate_portrait /
  *                              pptoaslib.rotate_portrait_full pplib.py:2338-2460,
  *                                                             pptoaslib.py:52-81
@@ -84,7 +90,7 @@
  *    reference's numpy rfft takes any length, pptoaslib.py:976-978)
  *    ppf_fit_portrait_batch, ppf_rotate_rows, ppf_scatter_rotate_rows,
  *    ppf_gaussian_portraits, ppf_spline_portraits,
- *    ppf_instrumental_response_rows, ppf_phase_shift_batch,
+ *    ppf_instrumental_response_rows, ppf_phase_shift_batch, ppf_phase_tau_batch,
  *    ppf_rotate_accumulate, ppf_rotate_fscrunch, ppf_irfft_rows, ppf_noise_rows and
  *    ppf_resid_chi2_rows run direct-sum kernels instead (O(nbin^2) per row;
  *    tests/test_gpu_generic_nbin.py), and so do the data-spectrum cache
@@ -343,6 +349,34 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin,
                           const double* data, const double* model,
                           const int32_t* model_idx, const double* noise,
                           int32_t Ns, double lo, double hi, double* out);
+
+/* ---------------------------------------------------------------------- */
+/* A phase and a scattering time per profile: fit_portrait_full             */
+/* (pptoaslib.py:928-1096) on each row as a one-channel portrait with       */
+/* fit_flags [1, 0, 0, 1, 0] and nu_fits = nu_outs = the channel's own      */
+/* frequency, by scipy's trust-ncg (gtol -1, maxiter 1000); one wave per    */
+/* profile (ppfit_nbscat.hip).  16 <= nbin <= 8192 (PPF_ERR_UNSUPPORTED     */
+/* otherwise).                                                              */
+/*   model[nmodel][nbin]: the unscattered template rows; model_idx[nprof]   */
+/*     (int32, or NULL: row 0) picks each profile's.                        */
+/*   noise[nprof]: time-domain sigma, or NaN / NULL -> get_noise_PS of the  */
+/*     row (pplib.py:2227-2253).                                            */
+/*   tau0[nprof] (or NULL): starting tau in rotations, linear; <= 0 or NaN  */
+/*     starts at 1 / nbin.  The starting phase is the peak of the           */
+/*     cross-correlation with the template scattered at the starting tau,   */
+/*     on min(nbin, 256) phases.                                            */
+/*   log10_tau != 0: the fitted parameter t is log10(tau), else tau.        */
+/*   out[nprof][9] = phi, phi_err, t, t_err, scale, scale_err, snr,         */
+/*     red_chi2 (dof nbin - 3), cov(phi, t).                                */
+/*   status[nprof], nfev[nprof] (int32): scipy's status code and its count  */
+/*     of objective evaluations.                                            */
+/* A profile's results do not depend on what shares the call.               */
+/* ---------------------------------------------------------------------- */
+int ppf_phase_tau_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin,
+                        const double* data, const double* model,
+                        const int32_t* model_idx, const double* noise,
+                        const double* tau0, int32_t log10_tau, double* out,
+                        int32_t* status, int32_t* nfev);
 
 /* Principal components of nport portraits (pplib.pca, pplib.py:1497-1534):
  * mean_prof[p] = sum_n w[p][n] port[p][n] / sum_n w[p][n] (channels in

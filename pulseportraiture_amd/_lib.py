@@ -95,6 +95,9 @@ EXPORTS = {
     "ppf_phase_shift_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                _dp, _dp, _dp, _dp, ctypes.c_int32,
                                ctypes.c_double, ctypes.c_double, _dp], ctypes.c_int),
+    "ppf_phase_tau_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                             _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp],
+                            ctypes.c_int),
     "ppf_rotate_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                          _dp], ctypes.c_int),
     "ppf_rotate_accumulate": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,

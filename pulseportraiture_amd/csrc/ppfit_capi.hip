@@ -1134,6 +1134,81 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const doubl
   });
 }
 
+int ppf_phase_tau_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const double* data,
+                        const double* model, const int32_t* model_idx, const double* noise,
+                        const double* tau0, int32_t log10_tau, double* out, int32_t* status,
+                        int32_t* nfev) {
+  if (!ctx || !data || !model || !out || !status || !nfev)
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nprof <= 0) return PPF_OK;
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // number of template rows = 1 + max(model_idx); the caller sizes model.
+  int nmodel = 1;
+  if (model_idx) {
+    std::vector<int32_t> h(nprof);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), model_idx, nprof * sizeof(int32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int32_t v : h) {
+      if (v < 0) return fail(ctx, PPF_ERR_INVALID, "negative model_idx");
+      nmodel = std::max(nmodel, (int)v + 1);
+    }
+  }
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  // the template rows' spectra once, then the profiles' in chunks of the
+  // workspace limit, each followed by its fits
+  const size_t NH = (size_t)nbin / 2 + 1, brow = NH * sizeof(double2);
+  if (int r = ensure(ctx, ctx->buf[kAux], (size_t)nmodel * brow)) return r;
+  double2* M = static_cast<double2*>(ctx->buf[kAux].p);
+  if (int r = timed(ctx, PPF_K_MODEL_FFT, [&] {
+        launch_rfft_rows(ctx->stream, logN, nbin, nmodel, model, M, tw);
+      }))
+    return r;
+  const int64_t chunk =
+      std::max<int64_t>(1, std::min<int64_t>(nprof, ctx->ws_limit / (int64_t)brow));
+  if (int r = ensure(ctx, ctx->buf[kWs], (size_t)chunk * brow)) return r;
+  double2* D = static_cast<double2*>(ctx->buf[kWs].p);
+  NbScatArgs na;
+  na.nbin = nbin;
+  na.NH = (int)NH;
+  na.kc = noise_kc(nbin);
+  na.log10_tau = log10_tau != 0;
+  na.D = D;
+  na.M = M;
+  const int nh = nbin / 2;  // harmonics 1 .. nh; 64 per register slot
+  const int nj = nh <= 64 ? 1 : nh <= 128 ? 2 : nh <= 256 ? 4 : nh <= 512 ? 8 : nh <= 1024 ? 16 : 0;
+  for (int64_t r0 = 0; r0 < nprof; r0 += chunk) {
+    const int nc = (int)std::min<int64_t>(chunk, nprof - r0);
+    if (int r = timed(ctx, PPF_K_DATA_XSPEC, [&] {
+          launch_rfft_rows(ctx->stream, logN, nbin, nc, data + (size_t)r0 * nbin, D, tw);
+        }))
+      return r;
+    na.nprof = nc;
+    na.model_idx = model_idx ? model_idx + r0 : nullptr;
+    na.noise = noise ? noise + r0 : nullptr;
+    na.tau0 = tau0 ? tau0 + r0 : nullptr;
+    na.out = out + (size_t)r0 * 9;
+    na.status = status + r0;
+    na.nfev = nfev + r0;
+    const dim3 g((nc + kWaves - 1) / kWaves), b(kBlock);
+    if (int r = timed(ctx, PPF_K_SOLVE, [&] {
+          switch (nj) {
+            case 1: hipLaunchKernelGGL(k_nbscat<1>, g, b, 0, ctx->stream, na); break;
+            case 2: hipLaunchKernelGGL(k_nbscat<2>, g, b, 0, ctx->stream, na); break;
+            case 4: hipLaunchKernelGGL(k_nbscat<4>, g, b, 0, ctx->stream, na); break;
+            case 8: hipLaunchKernelGGL(k_nbscat<8>, g, b, 0, ctx->stream, na); break;
+            case 16: hipLaunchKernelGGL(k_nbscat<16>, g, b, 0, ctx->stream, na); break;
+            default: hipLaunchKernelGGL(k_nbscat<0>, g, b, 0, ctx->stream, na); break;
+          }
+        }))
+      return r;
+  }
+  return PPF_OK;
+}
+
 int ppf_rotate_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* in,
                     const double* phase, double* out) {
   if (!ctx || !in || !phase || !out) return fail(ctx, PPF_ERR_INVALID, "null argument");

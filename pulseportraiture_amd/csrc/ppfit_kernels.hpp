@@ -63,6 +63,20 @@ struct PhaseShiftArgs {
   const double2* tw;
 };
 
+// k_nbscat (ppfit_nbscat.hip): one phase + tau fit per profile
+struct NbScatArgs {
+  int nprof, nbin, NH, kc;  // NH = nbin / 2 + 1, the row pitch of D and M
+  int log10_tau;
+  const double2* D;        // [nprof][NH] rfft of the profiles
+  const double2* M;        // [nmodel][NH] rfft of the template rows
+  const int* model_idx;    // [nprof] or null (row 0)
+  const double* noise;     // [nprof] or null (NaN -> get_noise_PS of the row)
+  const double* tau0;      // [nprof] or null: starting tau [rot], linear
+  double* out;             // [nprof][9]
+  int* status;             // [nprof]
+  int* nfev;               // [nprof]
+};
+
 // Taylor-moment cross-spectrum (phase-family fits, see ppfit_taylor.hip):
 // kMT moments T_m = sum_k v_k^m W_k per channel, v_k = k / N in [0, 1]; an
 // evaluation at per-channel offset y = 2 pi N delta uses terms m < kMTerm and
@@ -843,6 +857,9 @@ __global__ void k_model_spec_gen(const double* model, double2* M, double* pn, in
 __global__ void k_rotate_rows_gen(const double* in, const double* phase, const double* tau,
                                   double* out, const double2* tw, int nbin);
 __global__ void k_phase_shift_gen(PhaseShiftArgs a, int nbin);
+// NJ: 64-harmonic register slots a lane holds (64 NJ >= nbin / 2); 0: the
+// rows stay in memory (nbin > 2048)
+template <int NJ> __global__ void k_nbscat(NbScatArgs a);
 __global__ void k_rfft_rows_gen(const double* in, double2* spec, const double2* tw, int nbin);
 __global__ void k_irfft_rows_gen(const double2* spec, double* out, const double2* tw, int nbin);
 __global__ void k_noise_rows_gen(const double* in, double* out, int kc, const double2* tw, int nbin);

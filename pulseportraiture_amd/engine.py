@@ -554,6 +554,36 @@ class Engine:
         out._keep = (d, m, nz, mi)
         return out
 
+    def phase_tau_batch(self, data, model, noise=None, tau0=None, log10_tau=True,
+                        model_idx=None):
+        """A phase and a scattering time per row: fit_portrait_full
+        (pptoaslib.py:928-1096) on each row as a one-channel portrait with
+        fit_flags [1, 0, 0, 1, 0], one wave per row (ppf_phase_tau_batch).
+        model: the unscattered template rows; tau0: starting tau [rot], linear
+        (None or 0: 1 / nbin).  Returns (out [nprof, 9] float64 = phi, phi_err,
+        t, t_err, scale, scale_err, snr, red_chi2, cov(phi, t) with t = log10
+        tau or tau; status [nprof] int32; nfev [nprof] int32), device tensors."""
+        dev = self.device
+        d = _dev_f64(data, dev)
+        if d.dim() == 1:
+            d = d.unsqueeze(0)
+        nprof, nbin = d.shape
+        m = _dev_f64(model, dev)
+        if m.dim() == 1:
+            m = m.unsqueeze(0)
+        nz = None if noise is None else _bcast(noise, nprof, 1, dev).reshape(nprof).contiguous()
+        t0 = None if tau0 is None else _bcast(tau0, nprof, 1, dev).reshape(nprof).contiguous()
+        mi = None if model_idx is None else _dev_i32(model_idx, dev)
+        out = torch.empty(nprof, 9, dtype=torch.float64, device=dev)
+        status = torch.empty(nprof, dtype=torch.int32, device=dev)
+        nfev = torch.empty(nprof, dtype=torch.int32, device=dev)
+        self._chk(self.lib.ppf_phase_tau_batch(self.ctx, nprof, nbin, _ptr(d), _ptr(m),
+                                               _ptr(mi), _ptr(nz), _ptr(t0),
+                                               int(bool(log10_tau)), _ptr(out), _ptr(status),
+                                               _ptr(nfev)))
+        out._keep = (d, m, nz, t0, mi)
+        return out, status, nfev
+
     def rotate_rows(self, rows, phase, inplace=False):
         """irfft(rfft(row) e^{2 pi i k phase}) per row; inplace=True writes
         back into a contiguous float64 device tensor (each row is read whole
@@ -1254,7 +1284,7 @@ def _on_engine_stream(fn):
     return run
 
 
-for _name in ("fit_batch", "phase_shift_batch", "rotate_rows", "gaussian_portraits",
+for _name in ("fit_batch", "phase_shift_batch", "phase_tau_batch", "rotate_rows", "gaussian_portraits",
               "spline_portraits", "pca_portraits", "pca_project", "gauss_eval", "gauss_fit",
               "gauss_eval_join", "gauss_fit_join",
               "instrumental_response_rows",

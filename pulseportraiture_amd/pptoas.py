@@ -474,7 +474,28 @@ class GetTOAs:
         one ppf_phase_shift_batch call (brute force on linspace(-0.5, 0.5,
         100) + Nelder-Mead, pplib.py:2054-2100, with the load_data noise as
         err); TOAs, flags and the per-archive arrays follow the reference.
-        As there, fit_scat is accepted but not fitted (tau = 0).  Reference
+
+        fit_scat=True fits a phase and a scattering time per channel instead,
+        which the reference announces but leaves commented out
+        (pptoas.py:752-753, 982-988): pptoaslib.fit_portrait_full on each
+        channel as a one-channel portrait with fit_flags [1, 0, 0, 1, 0] and
+        nu_fits = nu_outs = the channel's frequency, all in one
+        ppf_phase_tau_batch call (one wave per profile, trust-ncg; any other
+        method raises NotImplementedError).  A .gmodel template is built
+        unscattered (pptoas.py:896-911).  The starting tau is scat_guess =
+        (tau [s], nu_ref, alpha) or else the .gmodel's TAU, scaled to each
+        channel's own frequency -- a deliberate departure from the reference's
+        set-up, which computes one value per subint at the fit frequency --
+        and 1 / nbin where that is 0, for log10 and linear tau alike; the
+        starting phase is the cross-correlation peak with the template
+        scattered at it (ppfit_nbscat.hip).  nfit is 2 and fit_flags [1, 1]
+        (one channel cannot constrain alpha); taus / tau_errs [nsub, nchan]
+        hold the fitted parameter (log10 tau or tau, in rotations at the
+        channel's frequency), covariances is [nsub, nchan, 2, 2], nfevals and
+        rcs are scipy's.  TOAs carry scat_time [us], (log10_)scat_time(_err)
+        and scat_ref_freq = the channel's frequency as get_TOAs writes them,
+        without a Doppler factor (this method applies none).
+        fit_scat=False is the reference's behaviour (tau = 0).  Reference
         quirks kept: channel_red_chi2s[isub] is set to the last channel's
         reduced chi2 for the whole row (pptoas.py:1011); channels whose
         template-archive weight is 0 are skipped (pptoas.py:966).  Where the
@@ -486,7 +507,12 @@ class GetTOAs:
         """
         if quiet is None:
             quiet = self.quiet
-        self.nfit = 1 + 2 * int(bool(fit_scat))
+        fit_scat = bool(fit_scat)
+        if fit_scat and method != "trust-ncg":
+            raise NotImplementedError(
+                "get_narrowband_TOAs(fit_scat=True) fits with method='trust-ncg' only, not %r"
+                % (method,))
+        self.nfit = 1 + int(fit_scat)
         self.fit_phi, self.fit_tau = True, fit_scat
         self.fit_flags = [int(self.fit_phi), int(self.fit_tau)]
         self.log10_tau = log10_tau if fit_scat else False
@@ -535,8 +561,12 @@ class GetTOAs:
                 skip = np.asarray(md.weights)[0] == 0  # pptoas.py:966
                 models = np.asarray(model)[None]
             else:
+                if fit_scat and src.kind == "gmodel":
+                    self.model_code, self.model_nu_ref = src.code, src.nu_ref
+                    self.gparams, self.alpha = np.copy(src.gparams), src.alpha
                 first, midx[ok] = row_keys(np.column_stack([data.freqs[ok], data.Ps[ok]]))
-                models = src.portraits(data.freqs[ok[first]], nbin, data.Ps[ok[first]])
+                models = src.portraits(data.freqs[ok[first]], nbin, data.Ps[ok[first]],
+                                       scattered=not fit_scat)
             if self._irf_active():
                 # modelx convolved per subint, with its P and the chan_bw of
                 # its ok channels (pptoas.py:920-926)
@@ -549,7 +579,25 @@ class GetTOAs:
             where = list(zip(isub.tolist(), ichan.tolist()))
             t0 = time.time()
             out = np.zeros((0, 6))
-            if len(rows):
+            tau_out = np.zeros((0, 3))  # t, t_err, cov(phi, t) per row under fit_scat
+            rc_out, nfev_out = np.zeros(0, dtype=int), np.zeros(0, dtype=int)
+            if len(rows) and fit_scat:
+                # the starting tau [rot] at each channel's own frequency
+                nu, P_row = data.freqs[isub, ichan], data.Ps[isub]
+                if scat_guess is not None:
+                    ts, tref, alpha_g = scat_guess
+                    tau0 = (ts / P_row) * (nu / tref) ** alpha_g
+                elif src.kind == "gmodel":
+                    tau0 = (self.gparams[1] / P_row) * (nu / self.model_nu_ref) ** self.alpha
+                else:
+                    tau0 = np.zeros(len(rows))
+                res, rc_d, nfev_d = get_engine().phase_tau_batch(
+                    rows, models.reshape(-1, nbin), noise=noise, tau0=tau0,
+                    log10_tau=self.log10_tau, model_idx=mrows)
+                res = res.cpu().numpy()
+                out, tau_out = res[:, [0, 1, 4, 5, 6, 7]], res[:, [2, 3, 8]]
+                rc_out, nfev_out = rc_d.cpu().numpy(), nfev_d.cpu().numpy()
+            elif len(rows):
                 out = get_engine().phase_shift_batch(
                     rows, models.reshape(-1, nbin), noise=noise, Ns=100, bounds=(-0.5, 0.5),
                     model_idx=mrows).cpu().numpy()
@@ -592,6 +640,19 @@ class GetTOAs:
                     flags["flux_err"] = pfle[isub, ichan]
                 if print_parangle:
                     flags["par_angle"] = data.parallactic_angles[isub]
+                if fit_scat:
+                    tau, tau_err, cov_pt = tau_out[j]
+                    taus[isub, ichan], tau_errs[isub, ichan] = tau, tau_err
+                    covariances[isub, ichan] = [[phase_err ** 2, cov_pt], [cov_pt, tau_err ** 2]]
+                    nfevals[isub, ichan], rcs[isub, ichan] = nfev_out[j], rc_out[j]
+                    if self.log10_tau:
+                        flags["scat_time"] = 10 ** tau * P * 1e6
+                        flags["log10_scat_time"] = tau + np.log10(P)
+                        flags["log10_scat_time_err"] = tau_err
+                    else:
+                        flags["scat_time"] = tau * P * 1e6
+                        flags["scat_time_err"] = tau_err * P * 1e6
+                    flags["scat_ref_freq"] = data.freqs[isub, ichan]
                 for k, v in addtnl_toa_flags.items():
                     flags[k] = v
                 self.TOA_list.append(TOA(name, data.freqs[isub, ichan], toa, toa_err,

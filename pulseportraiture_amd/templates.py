@@ -10,8 +10,8 @@ driver                P (TAU * nbin / P)     response: P, chan_bw      scattered
 get_TOAs              the subint's           the subint's P; |f[1] -   no under fit_scat (TAU 0,  frequency row (+ P when
  (pptoas.py:351-393)  (:355-358)             f[0]| of its ok channels  index 0.0, :368-374),      TAU != 0); with the response
                                              (:387-393)                else yes                   also chan_bw (+ P when DM)
-get_narrowband_TOAs   the subint's           the subint's P; ok        yes (fit_scat is not       (frequency row, P); with the
- (pptoas.py:888-926)  (:892-895)             channels (:920-926)       fitted there)              response the subint
+get_narrowband_TOAs   the subint's           the subint's P; ok        no under fit_scat          (frequency row, P); with the
+ (pptoas.py:888-926)  (:892-895)             channels (:920-926)       (:896-911), else yes       response the subint
 show_fit, get_        data.Ps.mean()         the subint's P; |f[1] -   no where the fitted tau    (frequency row, fitted
  channels_to_zap      (:1369-1371)           f[0]| of all channels     != 0 (:1372-1378), else    tau != 0); with the
  (pptoas.py:1356-88)                         (:1382-1388)              yes                        response the subint
