@@ -181,14 +181,18 @@ int ppf_set_pipeline(ppf_ctx* ctx, int32_t pieces);
  *   PPF_OPT_GUESS_WAVE   1: the single-wave guess kernel takes the subints it
  *                        covers (default); 0: every guess in k_guess.
  *   PPF_OPT_HBM_TABLES   1: the per-channel tables in HBM at every channel
- *                        count (default 0: only above PPF_LDS_NCHAN).       */
+ *                        count (default 0: only above PPF_LDS_NCHAN).
+ *   PPF_OPT_POST_WAVE    1: the single-wave post-fit kernel (k_post_w) takes
+ *                        the phase-family fits it covers (default); 0: every
+ *                        post-fit in k_post.                                */
 #define PPF_OPT_SCAT_GRAPH 0
 #define PPF_OPT_SCAT_SPLIT 1
 #define PPF_OPT_SCAT_TAIL 2
 #define PPF_OPT_FUSE_MOMENTS 3
 #define PPF_OPT_GUESS_WAVE 4
 #define PPF_OPT_HBM_TABLES 5
-#define PPF_NUM_OPTS 6
+#define PPF_OPT_POST_WAVE 6
+#define PPF_NUM_OPTS 7
 int ppf_set_option(ppf_ctx* ctx, int32_t option, int32_t value);
 int ppf_get_option(const ppf_ctx* ctx, int32_t option, int32_t* value);
 /* Upper bound on workspace bytes the context may hold (default 32 GiB). */
@@ -221,8 +225,8 @@ int ppf_selftest(ppf_ctx* ctx, int32_t* fails);
  * enabled, every k_fit_taylor workgroup adds its wall_clock64 ticks (100 MHz)
  * per phase into device counters: out[0] guess, [1] meta + first moments,
  * [2] centre selection incl. recentring, [3] objective sweeps, [4] trust-
- * region step, [8] recentring passes, [9] workgroups; every k_post
- * workgroup likewise: [16] meta + Sd, [17] nu_zero sums and solve, [18]
+ * region step, [8] recentring passes, [9] workgroups; every k_post or
+ * k_post_w workgroup likewise: [16] meta + Sd, [17] nu_zero sums and solve, [18]
  * outputs at nu_out + centre pick, [19] with-scales sweep, [20] inverses,
  * [21] per-channel errors + stores, [22] workgroups.  The call copies the
  * counters to out (if non-null), zeroes them and sets the enable state.   */

@@ -35,7 +35,7 @@ GAUSS_STATUS = {1: "converged: ftol", 2: "converged: xtol", 3: "converged: ftol 
                 -2: "non-finite residual"}
 # ppf_set_option ids (include/ppfit.h)
 OPTIONS = {"scat_graph": 0, "scat_split": 1, "scat_tail": 2, "fuse_moments": 3, "guess_wave": 4,
-           "hbm_tables": 5}
+           "hbm_tables": 5, "post_wave": 6}
 PPF_PHASE_N = 32
 
 _dp = ctypes.c_void_p  # device pointers travel as plain addresses

@@ -76,7 +76,7 @@ struct ppf_ctx {
   double* trace = nullptr;  // solver trace buffer (ppf_set_trace), device
   int trace_cap = 0;
   // launch-schedule options (ppf_set_option; include/ppfit.h)
-  int opt[PPF_NUM_OPTS] = {1, 1, 512, 1, 1, 0};
+  int opt[PPF_NUM_OPTS] = {1, 1, 512, 1, 1, 0, 1};
   double ktime[PPF_NUM_KERNELS] = {0};
   int64_t klaunch[PPF_NUM_KERNELS] = {0};
   // ppf_pca_gram_portraits under timing: mean pass, Gram tiles, slab sum, Jacobi, emit
@@ -490,10 +490,18 @@ int stage_taylor(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const F
   });
 }
 
+// The post-fit, PPF_K_POST whichever kernels run.  post_wave_ok depends on
+// launch-uniform values only, so exactly one of k_post_w and k_post<false> is
+// launched: the other would return for every subint.  k_post<true> (tau != 0
+// at the final point) is launched always: with tau not fitted that is the
+// start value init[.][3], which lives in device memory, and reading it back
+// would cost more than the empty launch.
 int stage_post(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const FitLaunch& L) {
   return timed_on(ctx, PPF_K_POST, st, [&] {
+    if (post_wave_ok(fa)) hipLaunchKernelGGL(k_post_w, dim3(n), dim3(64), L.lds_meta, st, fa);
     WIDE_SWITCH(L.wide, {
-      hipLaunchKernelGGL((k_post<false, WD>), dim3(n), dim3(kBlock), L.lds_meta, st, fa);
+      if (!post_wave_ok(fa))
+        hipLaunchKernelGGL((k_post<false, WD>), dim3(n), dim3(kBlock), L.lds_meta, st, fa);
       hipLaunchKernelGGL((k_post<true, WD>), dim3(n), dim3(kBlock), L.lds_meta, st, fa);
     });
   });
@@ -924,6 +932,7 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
 
   L.nbin = nbin;
   L.wide = wide;
+  fa.post_wave = ctx->opt[PPF_OPT_POST_WAVE] && !wide;  // k_post_w reads its tables from LDS
   L.lds_meta = wide ? 0 : meta_lds(nchan);
   L.lds_xspec = wide ? 0 : xspec_dyn_lds(nchan);
   // k_fit_taylor keeps moments [0, tnl) of T slot 0 in LDS (all of them when

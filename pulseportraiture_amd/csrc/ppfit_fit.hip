@@ -16,6 +16,7 @@
 // angle-addition recurrence and re-seeded exactly every 32 steps, so one
 // wave load instruction covers 8 full 128-byte segments of X.
 #include "ppfit_kernels.hpp"
+#include "ppfit_vthread.hpp"
 
 namespace ppf {
 
@@ -52,6 +53,7 @@ __device__ __forceinline__ size_t meta_bytes(int nchan) {
 }
 
 // refs = the subint's nu_fit (SolveState.refs, set by k_guess)
+template <int NT = kBlock>  // threads of the workgroup: kBlock, or 64 (k_post_w)
 __device__ Meta load_meta(const FitArgs& a, int c, int s, unsigned char* dyn, int* s_nok) {
   Meta m;
   const int nchan = a.nchan;
@@ -83,7 +85,7 @@ __device__ Meta load_meta(const FitArgs& a, int c, int s, unsigned char* dyn, in
   const double* refs = a.st[c].refs;
   const double r0 = 1.0 / (refs[0] * refs[0]);
   const double r1 = 1.0 / (refs[1] * refs[1]);
-  for (int j = tid; j < m.nok; j += kBlock) {
+  for (int j = tid; j < m.nok; j += NT) {
     const int n = m.chan[j];
     const double fr = a.freqs[(size_t)s * nchan + n];
     m.fr[j] = fr;
@@ -133,6 +135,31 @@ __device__ __forceinline__ void block_sum_vec(double (&v)[N], double (*red)[48])
     v[i] = t;
   }
   __syncthreads();
+}
+
+// The sums of a workgroup of NT threads that plays the block's threads as
+// virtual threads (ppfit_vthread.hpp): a thread runs its slots q = 0, 1, ...
+// one after the other, each over the items of block thread vt_thread(tid, q,
+// NT), and hands every slot's partial sums to vt_sum_vec / vt_sum with the
+// running totals (zero before slot 0).  NT = kBlock: one slot, block_sum_vec /
+// block_sum as they stand.  NT = 64: the slot's wave sum added to the total,
+// block_sum's operands in block_sum's order, with no LDS and no barrier.
+template <int NT, int N>
+__device__ __forceinline__ void vt_sum_vec(double (&v)[N], double (&tot)[N], double (*red)[48]) {
+  if constexpr (NT == kBlock) {
+    block_sum_vec(v, red);
+#pragma unroll
+    for (int i = 0; i < N; ++i) tot[i] = v[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) tot[i] += wave_sum(v[i]);
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ double vt_sum(double v, double tot, double* red) {
+  if constexpr (NT == kBlock) return block_sum(v, red);
+  else return tot + wave_sum(v);
 }
 
 // ---------------------------------------------------------------------------
@@ -582,14 +609,17 @@ __device__ __forceinline__ void taylor_cells(const TaylorSrc& ts, int n, int h, 
 }
 
 // Largest |y_n| of the fitted channels for evaluating prm (at refs) from the
-// centre ts; every thread gets it.  red: >= kWaves doubles of LDS.
+// centre ts; every thread gets it.  red: >= kWaves doubles of LDS.  (A
+// maximum does not depend on the order: any thread count gives the same.)
+template <int NT = kBlock>
 __device__ double taylor_reach(const Meta& m, const double* prm, const double* refs,
                                const TaylorSrc& ts, double P, double Ks, double* red) {
   double mx = 0.0;
-  for (int j = threadIdx.x; j < m.nok; j += kBlock)
+  for (int j = threadIdx.x; j < m.nok; j += NT)
     mx = fmax(mx, fabs(ts.same ? taylor_delta_lin(prm, ts.xc, m.d1[j], m.d2[j])
                                : taylor_delta(prm, refs, ts, m.fr[j], P)));
   mx = wave_max(mx);
+  if constexpr (NT == 64) return kTwoPi * Ks * mx;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) red[w] = mx;
   __syncthreads();
@@ -707,17 +737,24 @@ __device__ __forceinline__ void sweep_taylor0(const FitArgs& a, const Meta& m, c
 // each channel lane (h == 0) adds its terms into its own row of lrow
 // (kWaves * 8 rows of LDS) across groups and the block sums the rows once at
 // the end, instead of 45 wave reductions per channel group.
-template <int MODE, bool SCAT>
+// NT < kBlock (MODE 1, k_post_w): a workgroup of NT threads plays the block's
+// waves one slot after the other (ppfit_vthread.hpp).  Slot q's groups go into
+// the 8 rows per real wave of a small lrow, and the finished rows are added,
+// in row order, into the running totals before slot q + 1 starts: the block's
+// additions on the block's operands, with 8 live rows per wave instead of all.
+template <int MODE, bool SCAT, int NT = kBlock>
 __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, int s, const double* prm,
                       const double* refs, double P, double* acc_slot, double* out,
                       double (*red)[48], const TaylorSrc& ts, double (*lrow)[48] = nullptr) {
+  static_assert(NT == kBlock || (MODE == 1 && kBlock % NT == 0 && NT % 64 == 0),
+                "only the with-scales sweep runs on virtual waves");
   if constexpr (MODE == 0 && !SCAT) {
     if (ts.T && ts.same) {
       sweep_taylor0(a, m, prm, acc_slot, out, red, ts);
       return;
     }
   }
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, rw = tid >> 6;  // rw: the real wave
   const int g8 = lane >> 3, h = lane & 7;
   const int J = a.NHP >> 3;
   const bool log10_tau = a.log10_tau != 0;
@@ -727,99 +764,114 @@ __device__ __forceinline__ void sweep(const FitArgs& a, const Meta& m, int c, in
   const int fm = flag_mask(a);
   constexpr int NP = MODE == 0 ? 21 : 45;
   double* myrow = nullptr;
-  // (MODE 1 never reads red; it keeps the store because k_post<false> sits on
-  // the three-waves-per-SIMD register line, 168, and comes out at 170 without)
-  if (lane < NP) red[w][lane] = 0.0;
-  if constexpr (MODE == 1) {
-    myrow = lrow[w * 8 + g8];
-    if (h == 0)
-      for (int i = 0; i < NP; ++i) myrow[i] = 0.0;
-  }
-  __syncthreads();
   const int ngroups = (m.nok + 7) >> 3;
-  for (int gi = w; gi < ngroups; gi += kWaves) {
-    const int j = gi * 8 + g8;
-    const bool valid = j < m.nok;
-    const int jj = valid ? j : m.nok - 1;
-    const int n = m.chan[jj];
-    const double fr = m.fr[jj];
-    double acc[NACC];
-    if (!SCAT && ts.T) {
-      const double dl = ts.same ? taylor_delta_lin(prm, ts.xc, m.d1[jj], m.d2[jj])
-                                : taylor_delta(prm, refs, ts, fr, P);
-      taylor_cells(ts, n, h, dl, 0.5 * (double)a.nbin, acc);
-    } else if (!scat) {
-      const double phif = phase_frac(prm, fr, refs, P);
-      const double2* Xr = a.X + ((size_t)c * a.nchan + n) * a.NHP;
-      cells_phase(Xr, J, h, phif, acc);
-    } else {
-      const double phif = phase_frac(prm, fr, refs, P);
-      const double2* Xr = a.X + ((size_t)c * a.nchan + n) * a.NHP;
-      const double* M2r = a.M2 + ((size_t)midx * a.nchan + n) * a.NHP;
-      const double taun = tau_lin * pow(fr / refs[2], prm[4]);
-      cells_scat<PPF_SCAT_U>(Xr, M2r, J, h, phif, taun, acc);
+  // the slots (virtual waves per real wave) that have a group; one when the
+  // block itself runs
+  const int nslot = NT == kBlock ? 1 : vt_live_slots(ngroups, kWaves, NT / 64);
+  double tot = 0.0;  // NT < kBlock: column tid's sum over the finished slots' rows
+  for (int sl = 0; sl < nslot; ++sl) {
+    const int w = vt_wave(rw, sl, NT);
+    // (MODE 1 never reads red; it keeps the store because k_post<false> sits on
+    // the three-waves-per-SIMD register line, 168, and comes out at 170 without)
+    if constexpr (NT == kBlock)
+      if (lane < NP) red[w][lane] = 0.0;
+    if constexpr (MODE == 1) {
+      myrow = lrow[NT == kBlock ? ws_row(w, g8) : ws_local_row(rw, g8)];
+      if (h == 0)
+        for (int i = 0; i < NP; ++i) myrow[i] = 0.0;
     }
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) acc[i] = group8_sum(acc[i]);
-    if constexpr (MODE == 0) {
-      // f, g and H terms spread over each channel's 8 lanes: lane h forms
-      // out-slots h, h + 8, h + 16 (the channel's sums are on all 8 after
-      // group8_sum), then one chan8_sum per slot row sums the group's 8
-      // channels -- the additions wave_sum would make on one lane's 21 terms,
-      // on the same operands
-      const double dpre[2] = {m.d1[jj], m.d2[jj]};
-      const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[jj], m.iw2[jj], fr, prm, tau_lin, refs,
-                                       P, log10_tau, dpre);
-      const double q = d.C * d.C / d.S;
-      const LanePick L{d.dph[0], d.dph[1], d.dph[2], d.dts[0],
-                       d.dts[1], d.d2ts[0], d.d2ts[1], d.d2ts[2]};
-      if (h == 0 && valid) {
-        double* dst = acc_slot + (size_t)j * NACC;
-        for (int i = 0; i < NACC; ++i) dst[i] = acc[i];
+    __syncthreads();
+    for (int gi = ws_first_group(w); gi < ngroups; gi += kWaves) {
+      const int j = gi * 8 + g8;
+      const bool valid = j < m.nok;
+      const int jj = valid ? j : m.nok - 1;
+      const int n = m.chan[jj];
+      const double fr = m.fr[jj];
+      double acc[NACC];
+      if (!SCAT && ts.T) {
+        const double dl = ts.same ? taylor_delta_lin(prm, ts.xc, m.d1[jj], m.d2[jj])
+                                  : taylor_delta(prm, refs, ts, fr, P);
+        taylor_cells(ts, n, h, dl, 0.5 * (double)a.nbin, acc);
+      } else if (!scat) {
+        const double phif = phase_frac(prm, fr, refs, P);
+        const double2* Xr = a.X + ((size_t)c * a.nchan + n) * a.NHP;
+        cells_phase(Xr, J, h, phif, acc);
+      } else {
+        const double phif = phase_frac(prm, fr, refs, P);
+        const double2* Xr = a.X + ((size_t)c * a.nchan + n) * a.NHP;
+        const double* M2r = a.M2 + ((size_t)midx * a.nchan + n) * a.NHP;
+        const double taun = tau_lin * pow(fr / refs[2], prm[4]);
+        cells_scat<PPF_SCAT_U>(Xr, M2r, J, h, phif, taun, acc);
       }
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const double v = chan8_sum(valid ? mode0_term(d, L, q, h + 8 * r, fm) : 0.0);
-        const int t = (lane & 7) + 8 * r;
-        if (lane >= 8 && lane < 16 && t < NP) red[w][t] += v;
-      }
-    } else {
-      double ct[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i) ct[i] = 0.0;
-      if (h == 0 && valid) {
-        const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[j], m.iw2[j], fr, prm, tau_lin, refs, P,
-                                         log10_tau);
+      for (int i = 0; i < NACC; ++i) acc[i] = group8_sum(acc[i]);
+      if constexpr (MODE == 0) {
+        // f, g and H terms spread over each channel's 8 lanes: lane h forms
+        // out-slots h, h + 8, h + 16 (the channel's sums are on all 8 after
+        // group8_sum), then one chan8_sum per slot row sums the group's 8
+        // channels -- the additions wave_sum would make on one lane's 21 terms,
+        // on the same operands
+        const double dpre[2] = {m.d1[jj], m.d2[jj]};
+        const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[jj], m.iw2[jj], fr, prm, tau_lin, refs,
+                                         P, log10_tau, dpre);
         const double q = d.C * d.C / d.S;
-        const double sc = d.C / d.S;
-        double cross[5];
+        const LanePick L{d.dph[0], d.dph[1], d.dph[2], d.dts[0],
+                         d.dts[1], d.d2ts[0], d.d2ts[1], d.d2ts[2]};
+        if (h == 0 && valid) {
+          double* dst = acc_slot + (size_t)j * NACC;
+          for (int i = 0; i < NACC; ++i) dst[i] = acc[i];
+        }
 #pragma unroll
-        for (int i = 0; i < 5; ++i) cross[i] = -2.0 * (dC_(d, i) - sc * dS_(d, i));
-        double* dst = a.wsc + ((size_t)c * a.nchan + j) * 8;
-        dst[0] = sc;
-        dst[1] = d.S;
+        for (int r = 0; r < 3; ++r) {
+          const double v = chan8_sum(valid ? mode0_term(d, L, q, h + 8 * r, fm) : 0.0);
+          const int t = (lane & 7) + 8 * r;
+          if (lane >= 8 && lane < 16 && t < NP) red[w][t] += v;
+        }
+      } else {
+        double ct[NP];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) dst[2 + i] = cross[i];
-        const double ic = 1.0 / (2.0 * d.S);
+        for (int i = 0; i < NP; ++i) ct[i] = 0.0;
+        if (h == 0 && valid) {
+          const ChanDeriv d = derive<SCAT>(acc, scat, m.pn[j], m.iw2[j], fr, prm, tau_lin, refs, P,
+                                           log10_tau);
+          const double q = d.C * d.C / d.S;
+          const double sc = d.C / d.S;
+          double cross[5];
 #pragma unroll
-        for (int p = 0; p < 15; ++p) {
-          const int pi = pair_i(p), pj = pair_j(p);
-          if (a.flags[pi] && a.flags[pj]) {
-            ct[p] = -2.0 * q * ((d2C_(d, pi, pj) / d.C) - (0.5 * d2S_(d, pi, pj) / d.S));
-            ct[15 + p] = cross[pi] * cross[pj] * ic;
-            ct[30 + p] = Hn_(d, pi, pj);  // curvature without amplitude terms
+          for (int i = 0; i < 5; ++i) cross[i] = -2.0 * (dC_(d, i) - sc * dS_(d, i));
+          double* dst = a.wsc + ((size_t)c * a.nchan + j) * 8;
+          dst[0] = sc;
+          dst[1] = d.S;
+#pragma unroll
+          for (int i = 0; i < 5; ++i) dst[2 + i] = cross[i];
+          const double ic = 1.0 / (2.0 * d.S);
+#pragma unroll
+          for (int p = 0; p < 15; ++p) {
+            const int pi = pair_i(p), pj = pair_j(p);
+            if (a.flags[pi] && a.flags[pj]) {
+              ct[p] = -2.0 * q * ((d2C_(d, pi, pj) / d.C) - (0.5 * d2S_(d, pi, pj) / d.S));
+              ct[15 + p] = cross[pi] * cross[pj] * ic;
+              ct[30 + p] = Hn_(d, pi, pj);  // curvature without amplitude terms
+            }
           }
         }
-      }
-      if (h == 0 && valid)
+        if (h == 0 && valid)
 #pragma unroll
-        for (int i = 0; i < NP; ++i) myrow[i] += ct[i];
+          for (int i = 0; i < NP; ++i) myrow[i] += ct[i];
+      }
+    }
+    __syncthreads();
+    if constexpr (NT < kBlock) {
+      if (tid < NP)
+        for (int r = 0; r < (NT / 64) * 8; ++r) tot += lrow[r][tid];
+      __syncthreads();  // the next slot zeroes the rows again
     }
   }
-  __syncthreads();
   if (tid < NP) {
     double t = 0.0;
-    if constexpr (MODE == 0)
+    if constexpr (NT < kBlock)
+      t = tot;
+    else if constexpr (MODE == 0)
       for (int q = 0; q < kWaves; ++q) t += red[q][tid];
     else
       for (int r = 0; r < kWaves * 8; ++r) t += lrow[r][tid];
@@ -2100,15 +2152,16 @@ __device__ __forceinline__ int nz_nsums(int br) {
   }
 }
 
-// block_sum_vec over the first N of 22 sums
-template <int N>
-__device__ __forceinline__ void block_sum_first(double (&v)[22], double (*red)[48]) {
-  double u[N];
+// vt_sum_vec over the first N of 22 sums: the slot's sums v into the totals
+template <int N, int NT = kBlock>
+__device__ __forceinline__ void block_sum_first(double (&v)[22], double (&tot)[22],
+                                                double (*red)[48]) {
+  double u[N], t[N];
 #pragma unroll
-  for (int i = 0; i < N; ++i) u[i] = v[i];
-  block_sum_vec(u, red);
+  for (int i = 0; i < N; ++i) { u[i] = v[i]; t[i] = tot[i]; }
+  vt_sum_vec<NT>(u, t, red);
 #pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = u[i];
+  for (int i = 0; i < N; ++i) tot[i] = t[i];
 }
 
 // the positive root (sqrt of it when sq) closest to fmean
@@ -2196,12 +2249,13 @@ __device__ int nz_solve(int br, int option, const double* t, double* nz, PostWs&
   return 0;
 }
 
+template <int NT = kBlock>  // threads of the workgroup
 struct PostShared {
   PostWs ws;
-  double lrow[kWaves * 8][48];  // with-scales sweep: one row per channel lane
+  double lrow[(NT / 64) * 8][48];  // with-scales sweep: one row per channel lane
   double prm[5], refs[3], nu[3];
   double out[48];
-  double red[kWaves][48];
+  double red[NT / 64][48];
   double Xinv[25];
   double ifact[kMT];  // c_inv_fact for the Taylor sweep
   int ifit[5];
@@ -2210,9 +2264,12 @@ struct PostShared {
 };
 
 // zero-covariance frequencies, outputs at nu_out and the with-scales
-// covariance of one subint (all threads of the block)
-template <bool SCAT, bool W>  // W: one copy per k_post instantiation (its only caller)
-__device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, PostShared& sh) {
+// covariance of one subint (all threads of the workgroup).  NT = 64
+// (k_post_w): the wave plays the block's threads (ppfit_vthread.hpp) -- each
+// per-thread channel loop runs once per slot, and every sum gets the block's
+// operands in the block's order, so the outputs are bitwise the block's.
+template <bool SCAT, bool W, int NT = kBlock>  // W: one copy per k_post instantiation (its only caller)
+__device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, PostShared<NT>& sh) {
   const int tid = threadIdx.x;
   const int nchan = a.nchan;
   // diagnostic phase clock (ppf_phase_profile): thread 0 adds; the clock is
@@ -2226,13 +2283,15 @@ __device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, 
       t0 = t1;
     }
   };
-  const Meta m = load_meta(a, c, s, dyn, &sh.nok);
+  const Meta m = load_meta<NT>(a, c, s, dyn, &sh.nok);
   const SolveState& st = a.st[c];
   const double P = a.P[s];
   const bool log10_tau = a.log10_tau != 0;
+  // the slots of this thread that can hold a fitted channel (one for the block)
+  const int nslot = NT == kBlock ? 1 : vt_live_slots(m.nok, kBlock, NT);
   // zero the per-channel outputs of masked channels
   if (a.mask) {
-    for (int n = tid; n < nchan; n += kBlock) {
+    for (int n = tid; n < nchan; n += NT) {
       if (a.mask[(size_t)s * nchan + n]) continue;
       const size_t o = (size_t)s * nchan + n;
       a.o_scales[o] = 0.0;
@@ -2242,13 +2301,16 @@ __device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, 
   }
   // Sd (pptoaslib.py:985) and mean frequency of the fitted channels
   {
-    double v[2] = {0.0, 0.0};
-    for (int j = tid; j < m.nok; j += kBlock) {
-      v[0] += a.dsum[(size_t)c * nchan + m.chan[j]] * m.iw2[j];
-      v[1] += m.fr[j];
+    double tot[2] = {0.0, 0.0};
+    for (int q = 0; q < nslot; ++q) {
+      double v[2] = {0.0, 0.0};
+      for (int j = vt_thread(tid, q, NT); j < m.nok; j += kBlock) {
+        v[0] += a.dsum[(size_t)c * nchan + m.chan[j]] * m.iw2[j];
+        v[1] += m.fr[j];
+      }
+      vt_sum_vec<NT>(v, tot, sh.red);
     }
-    block_sum_vec(v, sh.red);
-    if (tid == 0) { sh.Sd = v[0]; sh.fmean = v[1] / (double)m.nok; }
+    if (tid == 0) { sh.Sd = tot[0]; sh.fmean = tot[1] / (double)m.nok; }
   }
   if (tid == 0) {
     sh.nfit = 0;
@@ -2285,23 +2347,29 @@ __device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, 
     double t[22];
     double sums[22];
     for (int i = 0; i < 22; ++i) sums[i] = 0.0;
-    if (br != NZ_NONE) {
-      const double tau_lin = log10_tau ? pow(10.0, st.x[3]) : st.x[3];
-      const bool scat = SCAT && tau_lin != 0.0;
-      for (int j = tid; j < m.nok; j += kBlock) {
-        const ChanDeriv d = derive<SCAT>(acc_fin + (size_t)j * NACC, scat, m.pn[j], m.iw2[j], m.fr[j],
-                                   st.x, tau_lin, sh.refs, P, log10_tau);
-        nz_terms(br, a.option, d, m.fr[j], sh.refs, fl, t);
-        for (int i = 0; i < 22; ++i) sums[i] += t[i];
+    for (int q = 0; q < nslot; ++q) {
+      double part[22];  // this slot's (virtual thread's) sums
+      for (int i = 0; i < 22; ++i) part[i] = 0.0;
+      if (br != NZ_NONE) {
+        const double tau_lin = log10_tau ? pow(10.0, st.x[3]) : st.x[3];
+        const bool scat = SCAT && tau_lin != 0.0;
+        for (int j = vt_thread(tid, q, NT); j < m.nok; j += kBlock) {
+          const ChanDeriv d = derive<SCAT>(acc_fin + (size_t)j * NACC, scat, m.pn[j], m.iw2[j], m.fr[j],
+                                     st.x, tau_lin, sh.refs, P, log10_tau);
+          nz_terms(br, a.option, d, m.fr[j], sh.refs, fl, t);
+          for (int i = 0; i < 22; ++i) part[i] += t[i];
+        }
       }
-    }
-    switch (nz_nsums(br)) {  // uniform across the block
-      case 2: block_sum_first<2>(sums, sh.red); break;
-      case 6: block_sum_first<6>(sums, sh.red); break;
-      case 8: block_sum_first<8>(sums, sh.red); break;
-      case 14: block_sum_first<14>(sums, sh.red); break;
-      case 22: block_sum_first<22>(sums, sh.red); break;
-      default: break;
+      // (the branches with tau or alpha fitted, 6 / 14 / 22 sums, never reach
+      // the one-wave kernel: post_wave_ok)
+      switch (nz_nsums(br)) {  // uniform across the block
+        case 2: block_sum_first<2, NT>(part, sums, sh.red); break;
+        case 6: if constexpr (NT == kBlock) block_sum_first<6, NT>(part, sums, sh.red); break;
+        case 8: block_sum_first<8, NT>(part, sums, sh.red); break;
+        case 14: if constexpr (NT == kBlock) block_sum_first<14, NT>(part, sums, sh.red); break;
+        case 22: if constexpr (NT == kBlock) block_sum_first<22, NT>(part, sums, sh.red); break;
+        default: break;
+      }
     }
     double* nz = sh.ws.nz;  // thread 0's, in LDS: no registers live across the root finder
     if (tid == 0) {
@@ -2356,14 +2424,14 @@ __device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, 
     for (int q = 0; q < 2; ++q) {
       if (!(st.mvalid & (1 << q))) continue;
       const TaylorSrc tq{a.T + ((size_t)c * 2 + q) * nchan * kMT, st.xc[q], st.refs};
-      const double y = taylor_reach(m, sh.prm, sh.nu, tq, P, Ks, sh.red[0]);
+      const double y = taylor_reach<NT>(m, sh.prm, sh.nu, tq, P, Ks, sh.red[0]);
       if (y < by) { by = y; best = q; }
     }
     ts = TaylorSrc{a.T + ((size_t)c * 2 + best) * nchan * kMT, st.xc[best], st.refs, false,
                    sh.ifact};
   }
   mark(18);
-  sweep<1, SCAT>(a, m, c, s, sh.prm, sh.nu, P, nullptr, sh.out, sh.red, ts, sh.lrow);
+  sweep<1, SCAT, NT>(a, m, c, s, sh.prm, sh.nu, P, nullptr, sh.out, sh.red, ts, sh.lrow);
   mark(19);
   if (tid == 0) {
     bool fit[5];
@@ -2412,37 +2480,40 @@ __device__ void post_subint(const FitArgs& a, int c, int s, unsigned char* dyn, 
   // ---- per-channel amplitude errors and S/N (pptoaslib.py:717-724, 1079-1082) ----
   const int nf = sh.nfit;
   double snr2 = 0.0;
-  for (int j = tid; j < m.nok; j += kBlock) {
-    const double* w = a.wsc + ((size_t)c * nchan + j) * 8;
-    const double sc = w[0], S = w[1];
-    const double ic = 1.0 / (2.0 * S);
-    // fitted parameters in order; Xinv is 0 outside the fitted block, and
-    // adding its zeros leaves the compact sums bitwise unchanged
-    double LL[5], U[5];
+  for (int vq = 0; vq < nslot; ++vq) {
+    double part = 0.0;  // this slot's (virtual thread's) sum
+    for (int j = vt_thread(tid, vq, NT); j < m.nok; j += kBlock) {
+      const double* w = a.wsc + ((size_t)c * nchan + j) * 8;
+      const double sc = w[0], S = w[1];
+      const double ic = 1.0 / (2.0 * S);
+      // fitted parameters in order; Xinv is 0 outside the fitted block, and
+      // adding its zeros leaves the compact sums bitwise unchanged
+      double LL[5], U[5];
 #pragma unroll
-    for (int q = 0; q < 5; ++q) U[q] = a.flags[q] ? w[2 + q] : 0.0;
+      for (int q = 0; q < 5; ++q) U[q] = a.flags[q] ? w[2 + q] : 0.0;
 #pragma unroll
-    for (int q = 0; q < 5; ++q) {
+      for (int q = 0; q < 5; ++q) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+          if (a.flags[i] && a.flags[q]) t += U[i] * sh.Xinv[i * 5 + q];
+        LL[q] = -ic * t;
+      }
       double t = 0.0;
 #pragma unroll
-      for (int i = 0; i < 5; ++i)
-        if (a.flags[i] && a.flags[q]) t += U[i] * sh.Xinv[i * 5 + q];
-      LL[q] = -ic * t;
+      for (int q = 0; q < 5; ++q)
+        if (a.flags[q]) t += LL[q] * U[q];
+      const double LR = -t * ic + ic;
+      const double csnr = sc * sqrt(S);
+      const int n = m.chan[j];
+      const size_t o = (size_t)s * nchan + n;
+      a.o_scales[o] = sc;
+      a.o_scale_errs[o] = sqrt(2.0 * LR);
+      a.o_channel_snrs[o] = csnr;
+      part += csnr * csnr;
     }
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-      if (a.flags[q]) t += LL[q] * U[q];
-    const double LR = -t * ic + ic;
-    const double csnr = sc * sqrt(S);
-    const int n = m.chan[j];
-    const size_t o = (size_t)s * nchan + n;
-    a.o_scales[o] = sc;
-    a.o_scale_errs[o] = sqrt(2.0 * LR);
-    a.o_channel_snrs[o] = csnr;
-    snr2 += csnr * csnr;
+    snr2 = vt_sum<NT>(part, snr2, sh.red[0]);
   }
-  snr2 = block_sum(snr2, sh.red[0]);
   if (tid == 0) {
     double* op = a.o_params + (size_t)s * 5;
     double* oe = a.o_param_errs + (size_t)s * 5;
@@ -2490,10 +2561,43 @@ template <bool SCAT, bool WIDE>
 #endif
 __global__ __launch_bounds__(kBlock, SCAT ? PPF_POST_SCAT_WG_PER_CU : PPF_POST_WG_PER_CU) void k_post(FitArgs a) {
   extern __shared__ __align__(16) unsigned char dyn[];
-  __shared__ PostShared sh;
+  __shared__ PostShared<> sh;
   const int c = blockIdx.x, s = a.sub0 + c;
   if ((a.st[c].scat_post != 0) != SCAT) return;
+  if constexpr (!SCAT)
+    if (post_wave_ok(a)) return;  // k_post_w's subints
   post_subint<SCAT, WIDE>(a, c, s, chan_tables<WIDE>(a, dyn), sh);
+}
+
+// ---------------------------------------------------------------------------
+// k_post_w: the phase-family post-fit of one subint per wave (64 threads), for
+// the fits post_wave_ok names (ppfit_kernels.hpp).  post_subint spends most of
+// a subint's time in thread 0's chain (the nu_zero solve, the outputs at
+// nu_out, two 5x5 inverses, the stores) and in loops that use nchan of the 256
+// threads, while four waves hold their registers.  Here one wave plays the
+// block's threads (ppfit_vthread.hpp), the same post_subint with NT = 64: every
+// sum has the block's operands in the block's order, so the outputs are
+// bitwise k_post<false>'s, and twelve subints fit a CU's registers and LDS
+// (3 KB of sweep rows, not 12: 5.9 KB static, 8.7 KB with the tables of 64
+// channels) where three did.  k_post<false> skips the subints taken here, as
+// k_guess does for k_guess_w.
+// ---------------------------------------------------------------------------
+// The launch bound's second figure is the waves per SIMD the compiler aims at.
+// Asked for 3 it takes 139 VGPRs; 4 and 5 fit only with spills (12 and 90
+// VGPRs); 12 is a target it cannot meet (and says so in a warning, as for
+// k_data_xspec<12>): it then holds register pressure lowest and ends at three
+// waves per SIMD, twelve subints per CU, with 143 VGPRs and no spills -- the
+// fastest of the four builds measured (headline / config 4 post-fit ms: 3:
+// 0.296 / 0.250, 4: 0.265 / 0.252, 5: 0.335 / 0.276, 12: 0.261 / 0.235).
+#ifndef PPF_POST_WAVE_OCC
+#define PPF_POST_WAVE_OCC 12  // A/B knob
+#endif
+__global__ __launch_bounds__(64, PPF_POST_WAVE_OCC) void k_post_w(FitArgs a) {
+  extern __shared__ __align__(16) unsigned char dyn[];
+  __shared__ PostShared<64> sh;
+  const int c = blockIdx.x, s = a.sub0 + c;
+  if (!post_wave_ok(a) || a.st[c].scat_post != 0) return;
+  post_subint<false, false, 64>(a, c, s, dyn, sh);
 }
 
 }  // namespace ppf

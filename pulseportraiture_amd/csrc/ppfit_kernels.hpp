@@ -132,7 +132,9 @@ struct FitArgs {
   int solver_flags;          // PPF_SOLVE_* / PPF_GUESS_* bits
   int method;                // PPF_METHOD_*
   int guess_wave;            // k_guess_w takes the subints it covers (guess_wave_ok)
-  const double2* X;          // chunk [c][nchan][NHP]
+  int post_wave;             // k_post_w takes the fits it covers (post_wave_ok): the
+                             // option, and the per-channel tables in LDS (not WIDE)
+  const double2* X;         // chunk [c][nchan][NHP]
   const double2* Dsp;        // chunk [c][nchan][NHP] data spectra (spec cache): the
                              // Taylor moment passes form X = D conj(M) from it
   const double2* R;          // chunk [c][NHP]
@@ -185,6 +187,23 @@ struct FitArgs {
   unsigned char* gdyn;       // WIDE kernels: [block][gdyn_stride] per-channel tables in HBM
   size_t gdyn_stride;
 };
+
+// The phase-family post-fits k_post_w takes in place of k_post<false>
+// (ppfit_fit.hip): tau and alpha not fitted (the zero-covariance sums of those
+// branches, up to 22 per thread, stay with the block), a Taylor-path fit (the
+// with-scales sweep from the moments: the shapes measured; an exact sweep
+// over X would run too, on a quarter of the lanes), the per-channel tables
+// in LDS, and at most kPostWaveNchan channels -- the count up to which one
+// wave per subint was measured faster than the block.  Masked
+// channels are allowed.  Launch-uniform: the host skips the launch that would
+// find no subint (stage_post), and each kernel tests it again.
+#ifndef PPF_POST_WAVE_NCHAN
+#define PPF_POST_WAVE_NCHAN 128
+#endif
+constexpr int kPostWaveNchan = PPF_POST_WAVE_NCHAN;
+__host__ __device__ inline bool post_wave_ok(const FitArgs& a) {
+  return a.post_wave && a.T && a.nchan <= kPostWaveNchan && !a.flags[3] && !a.flags[4];
+}
 
 // One solver-trace record (diagnostic, ppf_set_trace): the point, f, the
 // masked gradient and the 15 Hessian terms of one objective sweep, whether
@@ -957,5 +976,6 @@ template <bool SCAT, bool WIDE = false> __global__ void k_tnc(FitArgs a);
 template <bool SCAT, bool WIDE = false> __global__ void k_ncg(FitArgs a);
 __global__ void k_guess_w(FitArgs a);
 template <bool SCAT, bool WIDE = false> __global__ void k_post(FitArgs a);
+__global__ void k_post_w(FitArgs a);
 
 }  // namespace ppf

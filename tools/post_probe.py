@@ -1,5 +1,7 @@
 """In-kernel phase clocks of k_fit_taylor and k_post on the headline batch
-(ppf_phase_profile, wall_clock64 ticks at 100 MHz), per workgroup in us."""
+(ppf_phase_profile, wall_clock64 ticks at 100 MHz), per workgroup in us.
+
+  post_probe.py [NSUB [POST_WAVE]]   POST_WAVE 0: k_post<false>, 1: k_post_w (default)"""
 import sys
 
 import torch
@@ -10,6 +12,8 @@ from pulseportraiture_amd.engine import Engine  # noqa: E402
 
 nsub = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 eng = Engine(0)
+if len(sys.argv) > 2:
+    eng.set_option("post_wave", int(sys.argv[2]))
 dev = eng.device
 w = synth.make_workload(nsub, 64, 2048, seed=20240917)
 data = eng.synth(w.template, w.phase, w.sigma, w.seed, sub0=w.sub0)
