@@ -13,18 +13,20 @@ import numpy as np
 
 from oracle import ppfit_oracle as O
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nb_scat.npz")
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MAIN = "nb_scat.npz"     # make_golden_nb_scat.py: even lengths
+ODD = "nb_scat_odd.npz"  # make_golden_nb_scat_odd.py: nbin 999 and 2049
 FLAGS = [1, 0, 0, 1, 0]
 OUT_KEYS = ["phi", "phi_err", "tau", "tau_err", "scale", "scale_err", "snr", "red_chi2"]
 
 
-@functools.lru_cache(maxsize=1)
-def fixture():
-    return np.load(GOLDEN, allow_pickle=False)
+@functools.lru_cache(maxsize=None)
+def fixture(name=MAIN):
+    return np.load(os.path.join(GOLDEN_DIR, name), allow_pickle=False)
 
 
-def case(ic):
-    g = fixture()
+def case(ic, name=MAIN):
+    g = fixture(name)
     k = "c%d_" % ic
     c = {name[len(k):]: g[name] for name in g.files if name.startswith(k)}
     c["nbin"], c["log10"] = int(c["nbin"]), bool(c["log10"])
@@ -32,16 +34,16 @@ def case(ic):
     return c
 
 
-def ncase():
-    return int(fixture()["ncase"])
+def ncase(name=MAIN):
+    return int(fixture(name)["ncase"])
 
 
-def scattered_cases():
-    return [i for i in range(ncase()) if float(case(i)["tau_inj"]) != 0.0]
+def scattered_cases(name=MAIN):
+    return [i for i in range(ncase(name)) if float(case(i, name)["tau_inj"]) != 0.0]
 
 
-def unscattered_cases():
-    return [i for i in range(ncase()) if float(case(i)["tau_inj"]) == 0.0]
+def unscattered_cases(name=MAIN):
+    return [i for i in range(ncase(name)) if float(case(i, name)["tau_inj"]) == 0.0]
 
 
 def start_tau(tau0, nbin):

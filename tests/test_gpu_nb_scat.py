@@ -3,8 +3,9 @@ Engine.phase_tau_batch (ppf_phase_tau_batch, ppfit_nbscat.hip) and
 GetTOAs.get_narrowband_TOAs(fit_scat=True).
 
 References: the reference's own per-channel fits (tests/golden/nb_scat.npz,
-make_golden_nb_scat.py) and, for shapes the fixture does not hold, the CPU
-oracle run the same way (tests/nb_scat_cases.py; pinned to the fixture by
+make_golden_nb_scat.py; at the odd lengths 999 and 2049 nb_scat_odd.npz,
+make_golden_nb_scat_odd.py) and, for shapes the fixtures do not hold, the CPU
+oracle run the same way (tests/nb_scat_cases.py; pinned to the fixtures by
 tests/test_nb_scat_golden_cpu.py).
 
 Bars, per fitted channel: |dphi| <= 1e-3 phi_err and |dtau| <= 1e-3 tau_err
@@ -67,24 +68,53 @@ def check_rows(tag, out, status, nfev, ref):
     np.testing.assert_allclose(out[:, 7], ref["red_chi2"], rtol=1e-7, err_msg=tag)
 
 
-def oracle_rows(data, model, freqs, sigma, P, tau0, log10_tau):
-    """Per-row oracle fits from the bin-resolution cross-correlation start."""
+def kernel_start_phase(data, model, tau, nbin):
+    """The starting phase k_nbscat documents (header of ppfit_nbscat.hip): the
+    largest cross-correlation between the profile and the template scattered
+    at the starting tau, both limited to their first min(nbin / 2, 128)
+    harmonics, over the G = min(nbin, 256) phases -0.5 + g / G; the lowest g
+    on a tie (argmax)."""
+    G, K = min(nbin, 256), min(nbin // 2, 128)
+    from oracle import ppfit_oracle as O
+    B = O.scattering_portrait_FT(np.array([tau]), nbin)[0]
+    Y = (np.fft.rfft(data) * np.conj(np.fft.rfft(model) * B))[1:K + 1]
+    ph = -0.5 + np.arange(G) / G
+    corr = (Y[None] * np.exp(2j * np.pi * np.outer(ph, np.arange(1, K + 1)))).real.sum(axis=1)
+    return float(ph[np.argmax(corr)])
+
+
+def oracle_rows(data, model, freqs, sigma, P, tau0, log10_tau, start=NB.xcorr_phase):
+    """Per-row oracle fits from the bin-resolution cross-correlation start
+    (or, with start=kernel_start_phase, from the device's own)."""
     rows = []
     for n in range(len(data)):
         nbin = data.shape[-1]
-        ph0 = NB.xcorr_phase(data[n], model[n], NB.start_tau(float(tau0[n]), nbin), nbin)
+        ph0 = start(data[n], model[n], NB.start_tau(float(tau0[n]), nbin), nbin)
         rows.append(NB.oracle_channel(data[n], model[n], float(freqs[n]),
                                       None if sigma is None else float(sigma[n]), P, ph0,
                                       float(tau0[n]), log10_tau))
     return {k: np.array([r[k] for r in rows]) for k in rows[0]}
 
 
-@pytest.mark.parametrize("ic", NB.scattered_cases())
-def test_fixture_scattered_cases(eng, ic):
-    c = NB.case(ic)
+def fixture_case(eng, ic, name):
+    c = NB.case(ic, name)
     out, status, nfev = run(eng, c["data"], c["model"], c["errs"], c["tau0"], c["log10"],
                             np.arange(len(c["freqs"])))
     check_rows("case %d nbin %d log10 %d" % (ic, c["nbin"], c["log10"]), out, status, nfev, c)
+
+
+@pytest.mark.parametrize("ic", NB.scattered_cases())
+def test_fixture_scattered_cases(eng, ic):
+    fixture_case(eng, ic, NB.MAIN)
+
+
+@pytest.mark.parametrize("ic", NB.scattered_cases(NB.ODD))
+def test_fixture_odd_length_cases(eng, ic):
+    """The reference's own fits at nbin 999 (log10 tau, k_nbscat<8>) and 2049
+    (linear tau, k_nbscat<16>, the generic-length transform): no Nyquist term,
+    errs_FT = sigma sqrt(nbin / 2) with a half-integer, dof = nbin - 3."""
+    assert NB.case(ic, NB.ODD)["nbin"] % 2 == 1
+    fixture_case(eng, ic, NB.ODD)
 
 
 @pytest.mark.parametrize("ic", NB.unscattered_cases())
@@ -180,6 +210,121 @@ def test_smallest_and_largest_nbin(eng, nbin, width, tau, sigma):
     assert ref["snr"][0] >= 15.0, ref["snr"]
     out, status, nfev = run(eng, data, tmpl, noise, tau0, True)
     check_rows("nbin %d" % nbin, out, status, nfev, ref)
+
+
+# nbin, with nh = nbin // 2 and the register slots ppf_phase_tau_batch picks for
+# it (ppfit_capi.hip: nj = 1, 2, 4, 8, 16 for nh <= 64, 128, 256, 512, 1024,
+# else 0 = rows re-read from memory).  A change of that dispatch changes this
+# column: look again at which lengths sit on its seams.
+SEAM_NBINS = [
+    130,   # nh 65,   2 slots: one harmonic in the second slot
+    258,   # nh 129,  4 slots: third slot nearly empty, fourth empty
+    514,   # nh 257,  8 slots: first length of k_nbscat<8>
+    999,   # nh 499,  8 slots: odd, ragged
+    1024,  # nh 512,  8 slots: all eight full
+    1026,  # nh 513,  16 slots: nine of sixteen used
+    2049,  # nh 1024, 16 slots: odd, all sixteen full, generic transform
+    2050,  # nh 1025, 0: first length of the memory path
+    3000,  # nh 1500, 0: ragged tail (23 x 64 + 28)
+    4096,  # nh 2048, 0: power-of-two transform on the memory path
+    8191,  # nh 4095, 0: largest odd
+]
+# (nbin, log10_tau, noise given) at which the oracle starts from the kernel's
+# own starting phase (test_slot_and_length_seams)
+SEAM_KERNEL_START = {(2049, True, True)}
+
+
+@pytest.mark.parametrize("given", [True, False], ids=["noise_given", "noise_device"])
+@pytest.mark.parametrize("log10_tau", [True, False], ids=["log10", "linear"])
+@pytest.mark.parametrize("nbin", SEAM_NBINS)
+def test_slot_and_length_seams(eng, nbin, log10_tau, given):
+    """Every instantiation of k_nbscat, with full, partly filled and empty
+    slots, odd lengths and the memory path's first, ragged and longest
+    lengths, against the oracle (two rows a case; the noise given, or NaN and
+    estimated on the device, the oracle then with sigma=None).
+
+    The device starts from its coarse grid and the oracle from xcorr_phase.
+    At (2049, log10 tau, noise given) the oracle's own end point moves by
+    3.6e-6 sigma in phi and 4.5e-6 sigma in tau between those two starts (the
+    solver stops where rounding makes the predicted reduction non-positive),
+    and cov(phi, t), the small off-diagonal term, by 1.07e-6 of itself, past
+    its 1e-6 bar; the device differed from the xcorr-started oracle by exactly
+    those amounts, with equal status.  There the oracle starts from the
+    kernel's documented start (kernel_start_phase) and the bars are unchanged;
+    every other case keeps the xcorr start."""
+    width = max(0.004, 4.0 / nbin)
+    tau, sigma = 0.75 * width, 0.05
+    tmpl, data = gaussian_channel(nbin, width, tau, 0.137, sigma, 16 + nbin, nrow=2)
+    tau0 = np.full(2, 0.6 * tau)
+    start = kernel_start_phase if (nbin, log10_tau, given) in SEAM_KERNEL_START \
+        else NB.xcorr_phase
+    ref = oracle_rows(data, np.stack([tmpl] * 2), [1400.0] * 2, [sigma] * 2 if given else None,
+                      0.003, tau0, log10_tau, start)
+    assert ref["snr"].min() >= 15.0, ref["snr"]
+    noise = np.array([sigma] * 2) if given else np.full(2, np.nan)
+    out, status, nfev = run(eng, data, tmpl, noise, tau0, log10_tau)
+    check_rows("seam nbin %d log10 %d given %d" % (nbin, log10_tau, given), out, status, nfev,
+               ref)
+
+
+@pytest.mark.parametrize("log10_tau", [True, False], ids=["log10", "linear"])
+@pytest.mark.parametrize("nbin", [130, 258, 999, 2049, 3000])  # 2, 4, 8, 16 and 0 slots
+def test_upper_slots_carry_signal(eng, nbin, log10_tau):
+    """The seam cases' templates (width >= 0.004 rot) have no power above
+    harmonic ~150, so their upper slots hold noise only and bear on red_chi2
+    alone.  Here the template is half a bin wide and tau is two bins: |M_k| at
+    nbin / 4 is above 0.1 |M_1|, every slot's X_k, m_k and phasor bear on phi,
+    tau and their errors.  The coarse starting grid is then many bins from
+    the peak; the oracle starts from the kernel's documented start, and its
+    end point from xcorr_phase is the same to 4.8e-6 sigma."""
+    width, tau, sigma = 0.5 / nbin, 2.0 / nbin, 0.02
+    tmpl, data = gaussian_channel(nbin, width, tau, 0.137, sigma, 77 + nbin, nrow=2)
+    M = np.abs(np.fft.rfft(tmpl))
+    assert M[nbin // 4] >= 0.1 * M[1]
+    tau0 = np.full(2, 0.6 * tau)
+    ref = oracle_rows(data, np.stack([tmpl] * 2), [1400.0] * 2, [sigma] * 2, 0.003, tau0,
+                      log10_tau, kernel_start_phase)
+    assert ref["snr"].min() >= 15.0, ref["snr"]
+    out, status, nfev = run(eng, data, tmpl, np.array([sigma] * 2), tau0, log10_tau)
+    check_rows("sharp nbin %d log10 %d" % (nbin, log10_tau), out, status, nfev, ref)
+
+
+def test_more_than_one_chunk(eng):
+    """ppf_phase_tau_batch cuts its rows into chunks of the workspace limit
+    and offsets model_idx, noise, tau0, out, status and nfev by the chunk's
+    first row: 11 rows of the (256, linear) fixture case in one chunk, in
+    chunks of one and in chunks of 3, 3, 3, 2 are bitwise the same.  Every
+    per-row input differs from row to row, model_idx is not monotonic, and the
+    noise is given for some rows and NaN (estimated on the device) for others."""
+    c = linear_256_case()
+    nch, nbin = len(c["freqs"]), c["nbin"]
+    idx = (5 * np.arange(11)) % nch  # 0 5 10 15 4 9 14 3 8 13 2
+    assert len(set(idx)) == 11 and np.any(np.diff(idx) < 0)
+    noise = c["errs"][idx].copy()
+    est = np.array([1, 4, 6, 9])
+    noise[est] = np.nan
+    tau0 = c["tau0"][idx]
+    assert len(set(tau0)) == 11 and len(set(c["errs"][idx])) == 11
+    args = (c["data"][idx], c["model"], noise, tau0, False, idx)
+    per_row = (nbin // 2 + 1) * 16  # ppf_phase_tau_batch: one double2 spectrum a row
+    limit = eng.workspace_limit()
+    try:
+        whole = run(eng, *args)
+        eng.set_workspace_limit(1)  # max(1, ...): every row its own chunk
+        ones = run(eng, *args)
+        eng.set_workspace_limit(3 * per_row + per_row // 2)  # chunks of 3, 3, 3, 2
+        threes = run(eng, *args)
+    finally:
+        eng.set_workspace_limit(limit)
+    for name, a, b, d in zip(("out", "status", "nfev"), whole, ones, threes):
+        assert np.array_equal(a, b), name
+        assert np.array_equal(a, d), name
+    # the rows whose noise was given are the fixture's
+    giv = np.setdiff1d(np.arange(11), est)
+    check_rows("chunked rows, noise given", whole[0][giv], whole[1][giv], whole[2][giv],
+               {k: c[k][idx[giv]] for k in ("phi", "phi_err", "tau", "tau_err", "scale",
+                                            "scale_err", "snr", "red_chi2", "cov",
+                                            "return_code", "nfeval")})
 
 
 def test_shared_model_rows_and_device_noise(eng):

@@ -241,6 +241,182 @@ def test_get_red_chi2(gpu):
 
 
 # ---------------------------------------------------------------------------
+# more than one chunk of the workspace limit; more than 65,535 rows
+# ---------------------------------------------------------------------------
+def swt_row_bytes(nbin, L):
+    """Workspace a row takes (SwtPlan, ppfit_capi.hip): L levels of 2 nbin
+    doubles, L x (3 + 30 grid points) doubles, 16 bytes of per-row scalars and
+    64 of alignment slack; a chunk is limit / that, at least 1, at most 65,535
+    rows.  L is the deepest level of the whole call."""
+    return L * 2 * nbin * 8 + L * 33 * 8 + 16 + 64
+
+
+def at_limits(gpu, call, nbin, L):
+    """call() at the default limit, in chunks of one row (1 byte) and in
+    chunks of three; the limit is restored."""
+    limit = gpu.workspace_limit()
+    per_row = swt_row_bytes(nbin, L)
+    try:
+        whole = call()
+        gpu.set_workspace_limit(1)
+        ones = call()
+        gpu.set_workspace_limit(3 * per_row + per_row // 2)
+        threes = call()
+    finally:
+        gpu.set_workspace_limit(limit)
+    return whole, ones, threes
+
+
+CHUNK_LEVELS = [1, 3, 2, 5, 8, 4, 6, 7]  # the deepest in the second chunk of three
+# every row its own fact; where a fact with red_chi2 within 0.1 of 1 exists on a
+# 0.05 grid (rows 0, 1, 2, 3 and, hard, 5) it is one, so that the objective is
+# not 0 in the first two chunks of three
+CHUNK_FACTS = {"hard": [0.9, 1.95, 1.65, 0.15, 1.3, 0.3, 1.8, 2.05],
+               "soft": [0.4, 0.55, 0.45, 0.05, 1.3, 1.55, 1.8, 2.05]}
+
+
+def chunk_rows():
+    return np.stack([R.named_profile(256, s, 0.02) for s in range(1, 9)])
+
+
+@pytest.mark.parametrize("tt", ["hard", "soft"])
+def test_wavelet_smooth_more_than_one_chunk(gpu, tt):
+    """ppf_wavelet_smooth_rows offsets rows, nlevel, fact and out by the
+    chunk's first row and reuses the workspace slices: 8 rows with their own
+    level and fact in one chunk, in chunks of one and in chunks of 3, 3, 2 are
+    bitwise the same, and the last chunk's rows are the restatement's."""
+    rows = chunk_rows()
+    whole, ones, threes = at_limits(
+        gpu, lambda: gpu.wavelet_smooth_rows(rows, CHUNK_LEVELS, CHUNK_FACTS[tt],
+                                             tt).cpu().numpy(), 256, max(CHUNK_LEVELS))
+    assert np.array_equal(whole, ones)
+    assert np.array_equal(whole, threes)
+    for i in (6, 7):
+        ref = R.wavelet_smooth(rows[i], CHUNK_LEVELS[i], tt, CHUNK_FACTS[tt][i])
+        for y in (whole, ones, threes):
+            assert np.abs(y[i] - ref).max() <= TOL * np.abs(rows[i]).max(), (tt, i)
+        assert np.any(ref != rows[i])  # (the threshold did act)
+
+
+@pytest.mark.parametrize("tt", ["hard", "soft"])
+def test_wavelet_objective_more_than_one_chunk(gpu, tt):
+    """The same for ppf_wavelet_objective_rows (obj + r0, red_chi2 + r0, the
+    per-chunk noise slice)."""
+    rows = chunk_rows()
+
+    def call():
+        obj, rc = gpu.wavelet_objective_rows(rows, CHUNK_LEVELS, CHUNK_FACTS[tt], tt, 0.1)
+        return obj.cpu().numpy(), rc.cpu().numpy()
+    whole, ones, threes = at_limits(gpu, call, 256, max(CHUNK_LEVELS))
+    for k, name in enumerate(("objective", "red_chi2")):
+        assert np.array_equal(whole[k], ones[k]), name
+        assert np.array_equal(whole[k], threes[k]), name
+    print("%s: objective %s red_chi2 %s" % (tt, whole[0], whole[1]))
+    assert len(set(whole[1])) == 8  # every row's red chi2 is its own
+    ref = np.array([R.fit_wavelet_smooth_function(f, row, lev, tt)
+                    for row, lev, f in zip(rows, CHUNK_LEVELS, CHUNK_FACTS[tt])])
+    assert np.array_equal(whole[0] == 0.0, ref == 0.0)
+    assert np.count_nonzero(ref) == (5 if tt == "hard" else 4)
+
+
+def test_smart_smooth_more_than_one_chunk(gpu):
+    """ppf_smart_smooth_rows with the table: 8 rows at nbin 128, four levels;
+    row 4 is all zero (the second row of the second chunk of three, in the
+    slices a noisy profile, row 1, has just used): it stays zero with zero
+    table entries at every limit, and all six outputs are bitwise the same."""
+    rows = np.stack([R.named_profile(128, s, 0.05) for s in range(1, 9)])
+    rows[4] = 0.0
+
+    def call():
+        return [t.cpu().numpy() for t in gpu.smart_smooth_rows(rows, 4, table=True)]
+    whole, ones, threes = at_limits(gpu, call, 128, 4)
+    names = ("smooth", "nlevel", "fact", "red_chi2", "zeroed", "table")
+    for k, name in enumerate(names):
+        assert np.array_equal(whole[k], ones[k]), name
+        assert np.array_equal(whole[k], threes[k]), name
+    for res in (whole, ones, threes):
+        out = dict(zip(names, res))
+        assert out["table"].shape == (8, 4)
+        assert not np.any(out["smooth"][4]) and not np.any(out["table"][4])
+        assert out["nlevel"][4] == 0 and not out["zeroed"][4]
+        assert np.all(out["nlevel"][[0, 1, 2, 3, 5, 6, 7]] >= 1)
+        assert np.any(out["table"][1]) and np.any(out["table"][5])
+
+
+# five stable 16-bin profiles (as tests/test_swt_cpu.py defines stable: with
+# try_nlevels = 2 the restatement's threshold gap is at least 1.6e-2 and its
+# level gap at least 0.30; two choose level 1, three level 2, none is zeroed)
+ROWCAP_SEEDS = (1, 3, 5, 8, 9)
+# per-profile facts at level 1: the hard-threshold objective is not 0 at any of
+# them, and the nearest |coefficient| is 9e-3 of the threshold away
+ROWCAP_FACTS = [2.95, 63.0 / 29, 2.5, 2.9, 2.55]
+ROWCAP_NROW = 65538  # a chunk holds at most 65,535 rows: 65,535 + 3
+
+
+@pytest.fixture(scope="module")
+def rowcap():
+    five = np.stack([R.named_profile(16, s, 0.05) for s in ROWCAP_SEEDS])
+    i = np.arange(ROWCAP_NROW) % 5
+    return five, i, np.ascontiguousarray(five[i]), np.asarray(ROWCAP_FACTS)[i]
+
+
+def test_wavelet_smooth_past_the_row_cap(gpu, rowcap):
+    """65,538 rows of 16 bins at level 1: row i is bitwise row i % 5 of the
+    call on the five profiles alone, which is the restatement's."""
+    five, i, rows, facts = rowcap
+    small = gpu.wavelet_smooth_rows(five, 1, ROWCAP_FACTS).cpu().numpy()
+    for j in range(5):
+        y, lam, mags = R.wavelet_smooth(five[j], 1, "hard", ROWCAP_FACTS[j], details=True)
+        assert np.abs(mags - lam).min() >= 1e-6 * lam  # (the input condition)
+        assert np.abs(small[j] - y).max() <= TOL * np.abs(five[j]).max(), j
+    big = gpu.wavelet_smooth_rows(rows, 1, facts).cpu().numpy()
+    assert big.shape == (ROWCAP_NROW, 16)
+    assert np.array_equal(big, small[i])
+
+
+def test_wavelet_objective_past_the_row_cap(gpu, rowcap):
+    """The same for the objective.  Its bar at 16 bins is the module's recipe
+    on these inputs: 1e3 x the largest relative difference between the
+    restatement in float64 and in np.longdouble (measured at 3.8e-15, so
+    3.8e-12); red_chi2 to 1e-12 as in test_objective_matches_restatement."""
+    five, i, rows, facts = rowcap
+    obj, rc = [t.cpu().numpy() for t in gpu.wavelet_objective_rows(five, 1, ROWCAP_FACTS)]
+    ref = np.array([R.fit_wavelet_smooth_function(f, p, 1, full=True)
+                    for p, f in zip(five, ROWCAP_FACTS)], dtype=np.float64)
+    ref80 = np.array([R.fit_wavelet_smooth_function(f, p, 1, dtype=np.longdouble, full=True)
+                      for p, f in zip(five, ROWCAP_FACTS)])
+    assert np.all(ref[:, 0] != 0.0)
+    assert np.all(np.abs(np.abs(ref[:, 1] - 1.0) - 0.1) > 1e-9)
+    worst80 = float(np.abs(ref[:, 0] / ref80[:, 0] - 1).max())
+    err = np.abs(obj / ref[:, 0] - 1).max()
+    print("16 bins: float64 against longdouble %.3g, device against restatement %.3g"
+          % (worst80, err))
+    assert 0.0 < worst80 < 1e-12
+    assert err <= 1e3 * worst80
+    assert np.abs(rc - ref[:, 1]).max() <= 1e-12 * np.abs(ref[:, 1]).max()
+    big = [t.cpu().numpy() for t in gpu.wavelet_objective_rows(rows, 1, facts)]
+    assert big[0].shape == (ROWCAP_NROW,)
+    assert np.array_equal(big[0], obj[i]) and np.array_equal(big[1], rc[i])
+
+
+def test_smart_smooth_past_the_row_cap(gpu, rowcap):
+    """The same for smart_smooth_rows(try_nlevels=2, table=True), all six
+    outputs."""
+    five, i, rows, _ = rowcap
+    small = [t.cpu().numpy() for t in gpu.smart_smooth_rows(five, 2, table=True)]
+    for j in range(5):
+        ref = R.smart_smooth(five[j], try_nlevels=2, full=True)
+        assert int(small[1][j]) == ref["nlevel"] and bool(small[4][j]) == ref["zeroed"]
+        assert not ref["zeroed"]
+        assert np.abs(small[0][j] - ref["smooth"]).max() <= TOL * np.abs(five[j]).max(), j
+    assert set(small[1]) == {1, 2}
+    big = [t.cpu().numpy() for t in gpu.smart_smooth_rows(rows, 2, table=True)]
+    assert big[0].shape == (ROWCAP_NROW, 16) and big[5].shape == (ROWCAP_NROW, 2)
+    for a, b in zip(big, small):
+        assert np.array_equal(a, b[i])
+
+
+# ---------------------------------------------------------------------------
 # ppspline with smooth="swt"
 # ---------------------------------------------------------------------------
 NCHAN, NBIN, SNR_CUTOFF = 32, 256, 150.0
