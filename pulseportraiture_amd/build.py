@@ -28,7 +28,7 @@ DEPS = ["ppfit_lib.hip", "ppfit_spectra.hip", "ppfit_fit.hip", "ppfit_taylor.hip
         "ppfit_ncg.hip", "ppfit_models.hip", "ppfit_generic.hip", "ppfit_noisefit.hip", "ppfit_fscrunch.hip", "ppfit_fake.hip", "ppfit_pca.hip",
         "ppfit_gram.hip",
         "ppfit_gauss.hip", "ppfit_gbank.hip", "ppfit_swt.hip", "ppfit_nbscat.hip", "ppfit_capi.hip",
-        "ppfit_kernels.hpp", "ppfit_device.hpp", "ppfit_vthread.hpp"]
+        "ppfit_kernels.hpp", "ppfit_device.hpp", "ppfit_rowfft.hpp", "ppfit_vthread.hpp"]
 OUT = os.path.join(HERE, "libppfit.so")
 FITS_OUT = os.path.join(HERE, "libppfits.so")
 TIM_OUT = os.path.join(HERE, "libpptim.so")

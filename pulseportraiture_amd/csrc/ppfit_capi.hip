@@ -110,21 +110,14 @@ int ilog2_exact(int v) {
 }
 
 // Any nbin in [16, 8192]: *logN = log2(nbin / 2) selects the FFT kernels of
-// a power of two from 64 up, -1 the generic-length ones (ppfit_generic.hip)
-// for every other length.
+// a power of two from 64 up (RowPow2<logN>), -1 the direct sums (RowAny) for
+// every other length.
 int check_nbin_any(ppf_ctx* ctx, int nbin, int* logN) {
   if (nbin < 16 || nbin > 8192)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: outside [16, 8192]", nbin);
   const int l = ilog2_exact(nbin);
   *logN = l < 6 ? -1 : l - 1;
   return PPF_OK;
-}
-
-// dynamic LDS of the generic-length kernels
-size_t gen_row_lds(int nbin) { return (size_t)nbin * sizeof(double); }
-size_t gen_spec_lds(int nbin) { return (size_t)(nbin / 2 + 1) * sizeof(double2); }
-size_t gen_rot_lds(int nbin) {
-  return (((size_t)nbin * sizeof(double) + 15) & ~(size_t)15) + gen_spec_lds(nbin);
 }
 
 // the table of nbin in a cache (n cells, created by make on first use)
@@ -263,18 +256,35 @@ int resolve_timing(ppf_ctx* ctx) {
   return PPF_OK;
 }
 
-#define LOGN_SWITCH(L, BODY)                          \
-  switch (L) {                                        \
-    case 5: { constexpr int LG = 5; BODY; } break;    \
-    case 6: { constexpr int LG = 6; BODY; } break;    \
-    case 7: { constexpr int LG = 7; BODY; } break;    \
-    case 8: { constexpr int LG = 8; BODY; } break;    \
-    case 9: { constexpr int LG = 9; BODY; } break;    \
-    case 10: { constexpr int LG = 10; BODY; } break;  \
-    case 11: { constexpr int LG = 11; BODY; } break;  \
-    case 12: { constexpr int LG = 12; BODY; } break;  \
-    default: break;                                   \
+#define LOGN_SWITCH(L, ...)                                  \
+  switch (L) {                                               \
+    case 5: { constexpr int LG = 5; __VA_ARGS__; } break;    \
+    case 6: { constexpr int LG = 6; __VA_ARGS__; } break;    \
+    case 7: { constexpr int LG = 7; __VA_ARGS__; } break;    \
+    case 8: { constexpr int LG = 8; __VA_ARGS__; } break;    \
+    case 9: { constexpr int LG = 9; __VA_ARGS__; } break;    \
+    case 10: { constexpr int LG = 10; __VA_ARGS__; } break;  \
+    case 11: { constexpr int LG = 11; __VA_ARGS__; } break;  \
+    case 12: { constexpr int LG = 12; __VA_ARGS__; } break;  \
+    default: break;                                          \
   }
+
+// The row kernels (ppfit_rowfft.hpp): the body sees the policy as Row, the
+// kernel's last argument `row`, and lds(U), the dynamic LDS of a kernel that
+// declares Row::Lds<U>.
+#define ROW_SWITCH(L, NBIN, ...)                                             \
+  do {                                                                       \
+    if ((L) < 0) {                                                           \
+      using Row = RowAny;                                                    \
+      const Row row{NBIN};                                                   \
+      auto lds = [&](RowLds u) { return Row::lds(NBIN, u); };                \
+      __VA_ARGS__;                                                           \
+    } else {                                                                 \
+      LOGN_SWITCH(L, using Row = RowPow2<LG>; const Row row{};               \
+                  auto lds = [&](RowLds u) { return Row::lds(NBIN, u); };    \
+                  __VA_ARGS__)                                               \
+    }                                                                        \
+  } while (0)
 
 // WD: the instantiation with the per-channel tables in HBM (chan_tables)
 #define WIDE_SWITCH(W, ...)                                \
@@ -302,11 +312,9 @@ int model_spectra(ppf_ctx* ctx, int nrow, int nbin, const double* model, int zer
   double2* Mp = *M;
   double* pp = *pn;
   return timed(ctx, PPF_K_MODEL_FFT, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_model_spec_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin),
-                         ctx->stream, model, Mp, pp, NHP, zero_dc, tw, m2p, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_model_spec<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, model, Mp, pp, NHP, zero_dc, tw, m2p));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_model_spec<Row>, dim3(nrow), dim3(kBlock),
+                                              lds(kLdsRow), ctx->stream, model, Mp, pp, NHP,
+                                              zero_dc, tw, m2p, row));
   });
 }
 
@@ -316,36 +324,25 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 size_t meta_lds(int nchan) { return align256((size_t)nchan * (5 * sizeof(double) + sizeof(int))); }
 
 // ---------------------------------------------------------------------------
-// Row transforms that several entry points dispatch, nrow rows on st: the
-// generic-length kernel (logN < 0, ppfit_generic.hip) or the <LG> one, each
-// with its dynamic LDS.
+// Row transforms that several entry points dispatch, nrow rows on st.
 // ---------------------------------------------------------------------------
 void launch_rfft_rows(hipStream_t st, int logN, int nbin, int nrow, const double* in, double2* out,
                       const double2* tw) {
-  if (logN < 0)
-    hipLaunchKernelGGL(k_rfft_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin), st, in, out,
-                       tw, nbin);
-  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in, out,
-                                       tw));
+  ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_rfft_rows<Row>, dim3(nrow), dim3(kBlock),
+                                            lds(kLdsRow), st, in, out, tw, row));
 }
 
 void launch_irfft_rows(hipStream_t st, int logN, int nbin, int nrow, const double2* in,
                        double* out, const double2* tw) {
-  if (logN < 0)
-    hipLaunchKernelGGL(k_irfft_rows_gen, dim3(nrow), dim3(kBlock), gen_spec_lds(nbin), st, in, out,
-                       tw, nbin);
-  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_irfft_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in, out,
-                                       tw));
+  ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_irfft_rows<Row>, dim3(nrow), dim3(kBlock),
+                                            lds(kLdsSpec), st, in, out, tw, row));
 }
 
 // rotation by phase and / or scattering by tau (either may be null)
 void launch_rotate_rows(hipStream_t st, int logN, int nbin, int nrow, const double* in,
                         const double* phase, const double* tau, double* out, const double2* tw) {
-  if (logN < 0)
-    hipLaunchKernelGGL(k_rotate_rows_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin), st, in,
-                       phase, tau, out, tw, nbin);
-  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rotate_rows<LG>, dim3(nrow), dim3(kBlock), 0, st, in,
-                                       phase, tau, out, tw));
+  ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_rotate_rows<Row>, dim3(nrow), dim3(kBlock),
+                                            lds(kLdsRowInv), st, in, phase, tau, out, tw, row));
 }
 
 // ---------------------------------------------------------------------------
@@ -1096,6 +1093,22 @@ int ppf_selftest(ppf_ctx* ctx, int32_t* fails) {
   return PPF_OK;
 }
 
+// Number of template rows = 1 + max(model_idx) (device array or null: one
+// row); the caller sizes model.  A negative index is an error.
+static int count_model_rows(ppf_ctx* ctx, const int32_t* model_idx, int32_t nprof, int* nmodel) {
+  *nmodel = 1;
+  if (!model_idx) return PPF_OK;
+  std::vector<int32_t> h(nprof);
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), model_idx, nprof * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int32_t v : h) {
+    if (v < 0) return fail(ctx, PPF_ERR_INVALID, "negative model_idx");
+    *nmodel = std::max(*nmodel, (int)v + 1);
+  }
+  return PPF_OK;
+}
+
 int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const double* data,
                           const double* model, const int32_t* model_idx, const double* noise,
                           int32_t Ns, double lo, double hi, double* out) {
@@ -1105,18 +1118,8 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const doubl
   int logN;
   if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // number of template rows = 1 + max(model_idx); the caller sizes model.
-  int nmodel = 1;
-  if (model_idx) {
-    std::vector<int32_t> h(nprof);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), model_idx, nprof * sizeof(int32_t), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int32_t v : h) {
-      if (v < 0) return fail(ctx, PPF_ERR_INVALID, "negative model_idx");
-      nmodel = std::max(nmodel, (int)v + 1);
-    }
-  }
+  int nmodel;
+  if (int r = count_model_rows(ctx, model_idx, nprof, &nmodel)) return r;
   double2* M;
   double* pn;
   if (int r = model_spectra(ctx, nmodel, nbin, model, 1, ctx->buf[kAux], &M, &pn)) return r;
@@ -1135,11 +1138,8 @@ int ppf_phase_shift_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const doubl
   pa.out = out;
   pa.tw = tw;
   return timed(ctx, PPF_K_PHASE_SHIFT, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_phase_shift_gen, dim3(nprof), dim3(kBlock), gen_rot_lds(nbin),
-                         ctx->stream, pa, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_phase_shift<LG>, dim3(nprof), dim3(kBlock), 0,
-                                         ctx->stream, pa));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_phase_shift<Row>, dim3(nprof), dim3(kBlock),
+                                              lds(kLdsRowSpec), ctx->stream, pa, row));
   });
 }
 
@@ -1153,18 +1153,8 @@ int ppf_phase_tau_batch(ppf_ctx* ctx, int32_t nprof, int32_t nbin, const double*
   int logN;
   if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  // number of template rows = 1 + max(model_idx); the caller sizes model.
-  int nmodel = 1;
-  if (model_idx) {
-    std::vector<int32_t> h(nprof);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), model_idx, nprof * sizeof(int32_t), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int32_t v : h) {
-      if (v < 0) return fail(ctx, PPF_ERR_INVALID, "negative model_idx");
-      nmodel = std::max(nmodel, (int)v + 1);
-    }
-  }
+  int nmodel;
+  if (int r = count_model_rows(ctx, model_idx, nprof, &nmodel)) return r;
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   // the template rows' spectra once, then the profiles' in chunks of the
@@ -1413,11 +1403,8 @@ int ppf_noise_rows_frac(ppf_ctx* ctx, int32_t nrow, int32_t nbin, double frac, c
   // pplib.py:2245, kc = int((1 - frac**-1) * len(pows)); frac = 4 is noise_kc
   const int kc = (int)((1.0 - 1.0 / frac) * (double)(nbin / 2 + 1));
   return timed(ctx, PPF_K_NOISE, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_noise_rows_gen, dim3(nrow), dim3(kBlock), gen_row_lds(nbin),
-                         ctx->stream, in, out, kc, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, in, out, kc, tw));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_noise_rows<Row>, dim3(nrow), dim3(kBlock),
+                                              lds(kLdsRow), ctx->stream, in, out, kc, tw, row));
   });
 }
 
@@ -1437,12 +1424,9 @@ int ppf_noise_fit_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* i
   const double2* tw;
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   return timed(ctx, PPF_K_NOISE, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_noise_fit_rows_gen, dim3(nrow), dim3(kBlock),
-                         (size_t)(nbin + 2) * sizeof(double), ctx->stream, in, fact, noise_out,
-                         kc_out, idx_out, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_fit_rows<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, in, fact, noise_out, kc_out, idx_out, tw));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_noise_fit_rows<Row>, dim3(nrow), dim3(kBlock),
+                                              lds(kLdsSpec), ctx->stream, in, fact, noise_out,
+                                              kc_out, idx_out, tw, row));
   });
 }
 
@@ -1482,12 +1466,9 @@ int ppf_synth_portraits(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
   const int64_t rows = (int64_t)nsub * nchan;
   if (rows > 0x7fffffff) return fail(ctx, PPF_ERR_INVALID, "too many rows");
   return timed(ctx, PPF_K_SYNTH, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_synth_gen, dim3((unsigned)rows), dim3(kBlock), gen_spec_lds(nbin),
-                         ctx->stream, M, phase, data, nchan, NHP, sigma, seed, sub0, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_synth<LG>, dim3((unsigned)rows), dim3(kBlock), 0,
-                                         ctx->stream, M, phase, data, nchan, NHP, sigma, seed,
-                                         sub0, tw));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_synth<Row>, dim3((unsigned)rows), dim3(kBlock),
+                                              lds(kLdsSpec), ctx->stream, M, phase, data, nchan,
+                                              NHP, sigma, seed, sub0, tw, row));
   });
 }
 
@@ -1552,15 +1533,14 @@ int ppf_fake_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, in
     if (!fused) a.data = reinterpret_cast<double*>(static_cast<char*>(ctx->buf[kPack].p) + kPackHead);
   }
   if (int r = timed(ctx, PPF_K_SYNTH, [&] {
-        if (logN < 0) {
-          hipLaunchKernelGGL(k_fake_gen, dim3((unsigned)rows), dim3(kBlock), gen_spec_lds(nbin),
-                             ctx->stream, a, tw, nbin);
-        } else if (fused) {
-          LOGN_SWITCH(logN, hipLaunchKernelGGL((k_fake<LG, true>), dim3((unsigned)rows),
-                                               dim3(kBlock), 0, ctx->stream, a, tw));
+        if (fused) {  // power of two only
+          LOGN_SWITCH(logN, hipLaunchKernelGGL((k_fake<RowPow2<LG>, true>), dim3((unsigned)rows),
+                                               dim3(kBlock), 0, ctx->stream, a, tw,
+                                               RowPow2<LG>{}));
         } else {
-          LOGN_SWITCH(logN, hipLaunchKernelGGL((k_fake<LG, false>), dim3((unsigned)rows),
-                                               dim3(kBlock), 0, ctx->stream, a, tw));
+          ROW_SWITCH(logN, nbin, hipLaunchKernelGGL((k_fake<Row, false>), dim3((unsigned)rows),
+                                                    dim3(kBlock), lds(kLdsSpec), ctx->stream, a,
+                                                    tw, row));
         }
       }))
     return r;
@@ -1594,17 +1574,14 @@ int ppf_rotate_accumulate(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbi
   if (int r = ensure(ctx, ctx->buf[kAux], (size_t)nsplit * count * sizeof(double2))) return r;
   double2* partial = reinterpret_cast<double2*>(ctx->buf[kAux].p);
   if (int r = timed(ctx, PPF_K_ROT_ACCUM, [&] {
-        if (logN < 0)
-          hipLaunchKernelGGL(k_rot_accum_gen, dim3(nsplit * nchan), dim3(kBlock),
-                             gen_row_lds(nbin), ctx->stream, data, phase, weight, partial, nsub,
-                             nchan, nsplit, tw, nbin);
-        else if (wave)
+        if (wave)
           hipLaunchKernelGGL(k_rot_accum_w, dim3(nsplit * nchan), dim3(256), 0,
                              ctx->stream, data, phase, weight, partial, nsub, nchan, nsplit, tw);
         else
-          LOGN_SWITCH(logN, hipLaunchKernelGGL(k_rot_accum<LG>, dim3(nsplit * nchan),
-                                               dim3(kBlock), 0, ctx->stream, data, phase, weight,
-                                               partial, nsub, nchan, nsplit, tw));
+          ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_rot_accum<Row>, dim3(nsplit * nchan),
+                                                    dim3(kBlock), lds(kLdsRow), ctx->stream, data,
+                                                    phase, weight, partial, nsub, nchan, nsplit,
+                                                    tw, row));
       }))
     return r;
   double2* acc = reinterpret_cast<double2*>(accum);
@@ -1690,8 +1667,9 @@ int ppf_rotate_fscrunch(ppf_ctx* ctx, int32_t nunit, int32_t nchan, int32_t nbin
     const size_t count = (size_t)nu * NH;
     if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
           if (logN < 0)
-            hipLaunchKernelGGL(k_fscrunch_gen, dim3(grid), dim3(kBlock), gen_row_lds(nbin),
-                               ctx->stream, d, ph, w, partial, nchan, nslice, tw, nbin);
+            hipLaunchKernelGGL(k_fscrunch_gen, dim3(grid), dim3(kBlock),
+                               RowAny::lds(nbin, kLdsRow), ctx->stream, d, ph, w, partial, nchan,
+                               nslice, tw, RowAny{nbin});
           else if (wave)
             hipLaunchKernelGGL(k_fscrunch_w, dim3(grid), dim3(256), 0, ctx->stream, d, ph, w,
                                partial, nchan, nslice, tw);
@@ -1842,11 +1820,8 @@ int ppf_resid_chi2_rows(ppf_ctx* ctx, int32_t nrow, int32_t nbin, const double* 
   if (int r = twiddles(ctx, nbin, &tw)) return r;
   ResidArgs ra{data, phase, model, model_row, scale, tau, errs, dof, out};
   return timed(ctx, PPF_K_RESID, [&] {
-    if (logN < 0)
-      hipLaunchKernelGGL(k_resid_chi2_gen, dim3(nrow), dim3(kBlock), gen_rot_lds(nbin),
-                         ctx->stream, ra, tw, nbin);
-    LOGN_SWITCH(logN, hipLaunchKernelGGL(k_resid_chi2<LG>, dim3(nrow), dim3(kBlock), 0,
-                                         ctx->stream, ra, tw));
+    ROW_SWITCH(logN, nbin, hipLaunchKernelGGL(k_resid_chi2<Row>, dim3(nrow), dim3(kBlock),
+                                              lds(kLdsRowInv), ctx->stream, ra, tw, row));
   });
 }
 
@@ -2214,11 +2189,9 @@ void swt_launch_forward(ppf_ctx* ctx, const SwtArgs& a, int nr, int logN, int de
   hipLaunchKernelGGL(k_swt_median, dim3(a.L, nr), dim3(kBlock), 0, ctx->stream, a, deepest);
   if (!noise) return;
   double* out = const_cast<double*>(a.noise);
-  if (logN < 0)
-    hipLaunchKernelGGL(k_noise_rows_gen, dim3(nr), dim3(kBlock), gen_row_lds(a.nbin), ctx->stream,
-                       a.rows, out, a.kc, a.tw, a.nbin);
-  LOGN_SWITCH(logN, hipLaunchKernelGGL(k_noise_rows<LG>, dim3(nr), dim3(kBlock), 0, ctx->stream,
-                                       a.rows, out, a.kc, a.tw));
+  ROW_SWITCH(logN, a.nbin, hipLaunchKernelGGL(k_noise_rows<Row>, dim3(nr), dim3(kBlock),
+                                              lds(kLdsRow), ctx->stream, a.rows, out, a.kc, a.tw,
+                                              row));
 }
 
 }  // namespace

@@ -104,7 +104,10 @@ struct FakeEpi {
   double amp, sigma;
   uint64_t seed, gs;
   uint32_t cw;
-  __device__ __forceinline__ double2 operator()(int j, double2 v) const {
+  __device__ __forceinline__ bool active() const { return true; }  // amp
+  template <class V>
+  __device__ __forceinline__ double2 operator()(int j, V v0) const {
+    double2 v = v0;
     v.x *= amp;
     v.y *= amp;
     if (sigma != 0.0) {
@@ -140,85 +143,61 @@ __device__ __forceinline__ FakeEpi fake_row(const FakeArgs& a, size_t row, int* 
 }
 
 // data[s][p][n] = amp[s][n] irfft(Mfull_n e^{2 pi i k phase[s][n]}) + sigma[n] N(0,1), one
-// workgroup per row.  PACK: the row stays in LDS after the transform; its
-// extremes, the quantiser and the int16 stores follow (no fp64 row in HBM).
-template <int LOGN, bool PACK>
-__global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a, const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
+// workgroup per row.  PACK (RowPow2 only; the host packs RowAny's fp64 rows
+// with k_pack): the row stays in LDS after the transform; its extremes, the
+// quantiser and the int16 stores follow (no fp64 row in HBM).
+template <class Row, bool PACK>
+__global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a, const double2* __restrict__ tw,
+                                                 Row rw) {
+  __shared__ typename Row::template Lds<kLdsSpec> sm;
   __shared__ double red[2 * kWaves];
+  typename Row::Dev t(rw, sm, tw);
   const size_t row = blockIdx.x;
   const int tid = threadIdx.x;
   int n;
   double ph;
   const FakeEpi epi = fake_row(a, row, &n, &ph);
-  double2 xs[(N + kBlock) / kBlock + 1];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = tid + i * kBlock;
-    if (k <= N) xs[i] = cmul(a.M[(size_t)n * a.NHP + k], turn_phasor((double)k, ph));
-  }
-  if (!PACK) {
-    c2r_from_spectrum<LOGN>(buf, xs, tw, a.data + row * 2 * N, epi);
-    return;
-  }
-  c2r_in_lds<LOGN>(buf, xs, tw);
-  const double inv = 1.0 / (double)N;
-  double lo = INFINITY, hi = -INFINITY;
-  int nf = 0;
-  for (int j = tid; j < N; j += kBlock) {
-    const double2 v = epi(j, cscale(buf[j], inv));
-    buf[j] = v;
-    nf |= not_finite(v.x) | not_finite(v.y);
-    lo = fmin(lo, fmin(v.x, v.y));
-    hi = fmax(hi, fmax(v.x, v.y));
-  }
-  nf = __syncthreads_or(nf);  // every buf[j] is final past this barrier
-  if (nf) { lo = 0.0; hi = 0.0; }
-  block_minmax(lo, hi, red);
-  const RowQuant q(lo, hi);
-  if (tid == 0) {
-    a.scl[row] = q.scl;
-    a.offs[row] = q.offs;
-    if (nf) *a.bad = 1;
-  }
-  // two sample pairs (8 bytes of int16) per thread and store
-  short4* __restrict__ o4 = reinterpret_cast<short4*>(a.raw + row * 2 * N);
-  for (int j = 2 * tid; j < N; j += 2 * kBlock) {
-    const double2 u = buf[j], v = buf[j + 1];
-    o4[j >> 1] = nf ? make_short4(0, 0, 0, 0) : make_short4(q(u.x), q(u.y), q(v.x), q(v.y));
-  }
-}
-
-// k_fake for any nbin (k_synth_gen's direct sum; fp64 rows only -- the host
-// packs them with k_pack).  Dynamic LDS: nbin/2 + 1 double2.
-__global__ __launch_bounds__(kBlock) void k_fake_gen(FakeArgs a, const double2* __restrict__ tw,
-                                                     int nbin) {
-  extern __shared__ __align__(16) unsigned char gsm[];
-  double2* X = reinterpret_cast<double2*>(gsm);
-  const size_t row = blockIdx.x;
-  const int NH = nbin / 2 + 1;
-  int n;
-  double ph;
-  const FakeEpi epi = fake_row(a, row, &n, &ph);
-  for (int k = threadIdx.x; k < NH; k += kBlock)
-    X[k] = cmul(a.M[(size_t)n * a.NHP + k], turn_phasor((double)k, ph));
-  __syncthreads();
-  double* out = a.data + row * nbin;
-  idft_row(X, nbin, tw, out);
-  __syncthreads();  // the block's samples are stored (each pair is then one thread's)
-  for (int j = threadIdx.x; 2 * j < nbin; j += kBlock) {
-    const bool two = 2 * j + 1 < nbin;  // odd nbin: the last sample takes its pair's first normal
-    const double2 v = epi(j, cmk(out[2 * j], two ? out[2 * j + 1] : 0.0));
-    out[2 * j] = v.x;
-    if (two) out[2 * j + 1] = v.y;
+  typename Row::Own xs(t.spec);
+  t.for_bins([&](int i, int k) {
+    xs.at(i, k) = cmul(a.M[(size_t)n * a.NHP + k], turn_phasor((double)k, ph));
+  });
+  if constexpr (!PACK) {
+    t.inverse(xs, a.data + row * t.nbin(), epi);
+  } else {
+    constexpr int N = Row::N;
+    double2* buf = t.buf;
+    c2r_in_lds<Row::kLogN>(buf, xs.v, tw);
+    const double inv = 1.0 / (double)N;
+    double lo = INFINITY, hi = -INFINITY;
+    int nf = 0;
+    for (int j = tid; j < N; j += kBlock) {
+      const double2 v = epi(j, cscale(buf[j], inv));
+      buf[j] = v;
+      nf |= not_finite(v.x) | not_finite(v.y);
+      lo = fmin(lo, fmin(v.x, v.y));
+      hi = fmax(hi, fmax(v.x, v.y));
+    }
+    nf = __syncthreads_or(nf);  // every buf[j] is final past this barrier
+    if (nf) { lo = 0.0; hi = 0.0; }
+    block_minmax(lo, hi, red);
+    const RowQuant q(lo, hi);
+    if (tid == 0) {
+      a.scl[row] = q.scl;
+      a.offs[row] = q.offs;
+      if (nf) *a.bad = 1;
+    }
+    // two sample pairs (8 bytes of int16) per thread and store
+    short4* __restrict__ o4 = reinterpret_cast<short4*>(a.raw + row * 2 * N);
+    for (int j = 2 * tid; j < N; j += 2 * kBlock) {
+      const double2 u = buf[j], v = buf[j + 1];
+      o4[j >> 1] = nf ? make_short4(0, 0, 0, 0) : make_short4(q(u.x), q(u.y), q(v.x), q(v.y));
+    }
   }
 }
 
-#define PPF_INST_FAKE(L)                                                \
-  template __global__ void k_fake<L, false>(FakeArgs, const double2*);  \
-  template __global__ void k_fake<L, true>(FakeArgs, const double2*);
+#define PPF_INST_FAKE(L)                                                                     \
+  template __global__ void k_fake<RowPow2<L>, false>(FakeArgs, const double2*, RowPow2<L>);  \
+  template __global__ void k_fake<RowPow2<L>, true>(FakeArgs, const double2*, RowPow2<L>);
 PPF_INST_FAKE(5)
 PPF_INST_FAKE(6)
 PPF_INST_FAKE(7)
@@ -227,5 +206,6 @@ PPF_INST_FAKE(9)
 PPF_INST_FAKE(10)
 PPF_INST_FAKE(11)
 PPF_INST_FAKE(12)
+template __global__ void k_fake<RowAny, false>(FakeArgs, const double2*, RowAny);
 
 }  // namespace ppf

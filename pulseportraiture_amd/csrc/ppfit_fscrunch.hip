@@ -165,32 +165,30 @@ __global__ __launch_bounds__(256, 2) void k_fscrunch_w(const double* __restrict_
   }
 }
 
-// The same for any nbin (dft_bin, ppfit_generic.hip): thread t sums harmonics
+// The same for any nbin (RowAny's direct sums): thread t sums harmonics
 // k = t, t + kBlock, ... in channel order, in its own cells of the partial
-// spectrum.  Dynamic LDS: nbin doubles.
+// spectrum (k_rot_accum<RowAny>'s loop, over channels).  Dynamic LDS:
+// RowAny::lds(nbin, kLdsRow).
 __global__ __launch_bounds__(kBlock) void k_fscrunch_gen(const double* __restrict__ data,
                                                          const double* __restrict__ phase,
                                                          const double* __restrict__ weight,
                                                          double2* __restrict__ partial, int nchan,
                                                          int nslice,
                                                          const double2* __restrict__ tw,
-                                                         int nbin) {
-  extern __shared__ __align__(16) unsigned char gsm[];
-  double* x = reinterpret_cast<double*>(gsm);
-  const int u = blockIdx.x / nslice, p = blockIdx.x % nslice, NH = nbin / 2 + 1;
+                                                         RowAny rw) {
+  __shared__ RowAny::Lds<kLdsRow> sm;
+  RowAny::Dev t(rw, sm, tw);
+  const int u = blockIdx.x / nslice, p = blockIdx.x % nslice;
   const int n0 = p * kFsSlice, n1 = min(nchan, n0 + kFsSlice);
-  double2* out = partial + (size_t)blockIdx.x * NH;
-  for (int k = threadIdx.x; k < NH; k += kBlock) out[k] = cmk(0.0, 0.0);
+  RowAny::Own acc(partial + (size_t)blockIdx.x * t.nh());
+  t.for_bins([&](int i, int k) { acc.at(i, k) = cmk(0.0, 0.0); });
   for (int n = n0; n < n1; ++n) {
     const size_t row = (size_t)u * nchan + n;
     const double w = weight[row];
     if (w == 0.0) continue;  // uniform per block
-    __syncthreads();
-    load_real_row(x, data + row * nbin, nbin);
-    __syncthreads();
-    const double ph = phase[row];
-    for (int k = threadIdx.x; k < NH; k += kBlock)
-      out[k] = cadd(out[k], cscale(cmul(dft_bin(x, nbin, k, tw), turn_phasor((double)k, ph)), w));
+    t.load(data + row * t.nbin());
+    rot_add(t, acc, phase[row], w);
+    t.release();
   }
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "ppfit.h"
 #include "ppfit_device.hpp"
+#include "ppfit_rowfft.hpp"
 
 namespace ppf {
 
@@ -843,65 +844,52 @@ struct ResidArgs {
 // kernel declarations
 // ---------------------------------------------------------------------------
 __global__ void k_twiddles(double2* tw, int nbin);
-template <int LOGN>
+// row kernels: Row = RowPow2<LOGN> or RowAny (ppfit_rowfft.hpp)
+template <class Row>
 __global__ void k_model_spec(const double* model, double2* M, double* pn, int NHP, int zero_dc,
-                             const double2* tw, double* M2);
+                             const double2* tw, double* M2, Row row);
 template <int LOGN, bool WIDE = false> __global__ void k_data_xspec(SpecArgs a);
-template <int LOGN> __global__ void k_phase_shift(PhaseShiftArgs a);
-template <int LOGN>
+template <class Row> __global__ void k_phase_shift(PhaseShiftArgs a, Row row);
+template <class Row>
 __global__ void k_rotate_rows(const double* in, const double* phase, const double* tau,
-                              double* out, const double2* tw);
-template <int LOGN>
-__global__ void k_irfft_rows(const double2* spec, double* out, const double2* tw);
-template <int LOGN>
-__global__ void k_noise_rows(const double* in, double* out, int kc, const double2* tw);
-template <int LOGN>
+                              double* out, const double2* tw, Row row);
+template <class Row>
+__global__ void k_rfft_rows(const double* in, double2* spec, const double2* tw, Row row);
+template <class Row>
+__global__ void k_irfft_rows(const double2* spec, double* out, const double2* tw, Row row);
+template <class Row>
+__global__ void k_noise_rows(const double* in, double* out, int kc, const double2* tw, Row row);
+template <class Row>
 __global__ void k_synth(const double2* Mfull, const double* phase, double* data, int nchan,
-                        int NHP, double sigma, uint64_t seed, int64_t sub0, const double2* tw);
-template <int LOGN>
+                        int NHP, double sigma, uint64_t seed, int64_t sub0, const double2* tw,
+                        Row row);
+template <class Row>
 __global__ void k_rot_accum(const double* data, const double* phase, const double* weight,
                             double2* partial, int nsub, int nchan, int nsplit,
-                            const double2* tw);
+                            const double2* tw, Row row);
 __global__ void k_rot_accum_w(const double* data, const double* phase, const double* weight,
                               double2* partial, int nsub, int nchan, int nsplit, const double2* tw);
 __global__ void k_rot_accum_spec(const double2* spec, const double* phase, const double* weight,
                                  double2* partial, int nsub, int nchan, int nsplit, int N,
                                  int NHP);
 __global__ void k_accum_reduce(const double2* partial, double2* accum, int nsplit, size_t count);
-template <int LOGN> __global__ void k_resid_chi2(ResidArgs a, const double2* tw);
+template <class Row> __global__ void k_resid_chi2(ResidArgs a, const double2* tw, Row row);
 __global__ void k_vpow(double2* vp, int nbin, int rows);
-// any nbin (ppfit_generic.hip)
-__global__ void k_model_spec_gen(const double* model, double2* M, double* pn, int NHP, int zero_dc,
-                                 const double2* tw, double* M2, int nbin);
-__global__ void k_rotate_rows_gen(const double* in, const double* phase, const double* tau,
-                                  double* out, const double2* tw, int nbin);
-__global__ void k_phase_shift_gen(PhaseShiftArgs a, int nbin);
 // NJ: 64-harmonic register slots a lane holds (64 NJ >= nbin / 2); 0: the
 // rows stay in memory (nbin > 2048)
 template <int NJ> __global__ void k_nbscat(NbScatArgs a);
-__global__ void k_rfft_rows_gen(const double* in, double2* spec, const double2* tw, int nbin);
-__global__ void k_irfft_rows_gen(const double2* spec, double* out, const double2* tw, int nbin);
-__global__ void k_noise_rows_gen(const double* in, double* out, int kc, const double2* tw, int nbin);
-__global__ void k_rot_accum_gen(const double* data, const double* phase, const double* weight,
-                                double2* partial, int nsub, int nchan, int nsplit,
-                                const double2* tw, int nbin);
 // get_noise_fit / find_kc (ppfit_noisefit.hip)
-template <int LOGN>
+template <class Row>
 __global__ void k_noise_fit_rows(const double* in, double fact, double* noise, int* kc_out,
-                                 int* idx_out, const double2* tw);
-__global__ void k_noise_fit_rows_gen(const double* in, double fact, double* noise, int* kc_out,
-                                     int* idx_out, const double2* tw, int nbin);
+                                 int* idx_out, const double2* tw, Row row);
 template <int FN>
 __global__ void k_find_kc_rows(const double* pows, const double* errs, int n, int* kc_out,
                                int* idx_out);
-__global__ void k_resid_chi2_gen(ResidArgs a, const double2* tw, int nbin);
+// the fit's data pass for any nbin (ppfit_generic.hip)
 template <bool LTW>
 __global__ void k_dft_rows_mfma(const double* rows, double2* D, int nrows, int nbin, int NHP,
                                 const double2* tw);
 __global__ void k_data_post_gen(SpecArgs a, int nbin);
-__global__ void k_synth_gen(const double2* Mfull, const double* phase, double* data, int nchan,
-                            int NHP, double sigma, uint64_t seed, int64_t sub0,
-                            const double2* tw, int nbin);
 // ppf_rotate_fscrunch (ppfit_fscrunch.hip): channels per workgroup, a
 // constant of the build (the order of summation may not depend on the call)
 constexpr int kFsSlice = 32;
@@ -912,7 +900,7 @@ __global__ void k_fscrunch_w(const double* data, const double* phase, const doub
                              double2* partial, int nchan, int nslice, const double2* tw);
 __global__ void k_fscrunch_gen(const double* data, const double* phase, const double* weight,
                                double2* partial, int nchan, int nslice, const double2* tw,
-                               int nbin);
+                               RowAny row);
 __global__ void k_fscrunch_reduce(const double2* partial, double2* spec, int nslice, int NH,
                                   int nyq, size_t count);
 // ppf_fake_subints / ppf_pack_subints (ppfit_fake.hip)
@@ -930,8 +918,7 @@ struct FakeArgs {
   double* offs;
   int* bad;             // set to 1 by a row with a non-finite sample
 };
-template <int LOGN, bool PACK> __global__ void k_fake(FakeArgs a, const double2* tw);
-__global__ void k_fake_gen(FakeArgs a, const double2* tw, int nbin);
+template <class Row, bool PACK> __global__ void k_fake(FakeArgs a, const double2* tw, Row row);
 __global__ void k_pack(const double* data, int nbin, short* raw, double* scl, double* offs,
                        int* bad);
 __global__ void k_gauss_port(GaussArgs g, const double* freqs, double* out);

@@ -224,75 +224,34 @@ __device__ __forceinline__ void nf_finish(const double* pows, int NH, int kc, in
   }
 }
 
-// get_noise_fit per row, nbin = 2^(LOGN + 1).  The row's LDS buffer is reused:
-// once every thread holds its powers in registers, pows[NH] and d[NH] take
-// the place of the transformed row (2 NH = nbin + 2 doubles).
-template <int LOGN>
+// get_noise_fit per row.  The row's LDS buffer is reused: once every thread
+// holds its powers in registers, pows[NH] and d[NH] take the place of the
+// row (2 NH doubles: kLdsSpec).
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_noise_fit_rows(const double* __restrict__ in,
                                                            double fact,
                                                            double* __restrict__ noise,
                                                            int* __restrict__ kc_out,
                                                            int* __restrict__ idx_out,
-                                                           const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN, NH = N + 1;
-  constexpr int KI = (NH + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
+                                                           const double2* __restrict__ tw,
+                                                           Row row) {
+  constexpr int KI = Row::kMaxKI;
+  __shared__ typename Row::template Lds<kLdsSpec> sm;
   __shared__ NoiseFitShared sh;
-  const int r = blockIdx.x;
-  load_row<LOGN>(buf, in + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, nbin = t.nbin(), NH = t.nh();
+  t.load(in + (size_t)r * nbin);
   double pv[KI];
 #pragma unroll
   for (int i = 0; i < KI; ++i) {
     const int k = threadIdx.x + i * kBlock;
-    pv[i] = k < NH ? cabs2(rfft_post<LOGN>(buf, k, tw)) / (double)(2 * N) : 0.0;
+    pv[i] = k < NH ? cabs2(t.bin(k)) / (double)nbin : 0.0;
   }
-  __syncthreads();
-  double* pows = reinterpret_cast<double*>(buf);
+  t.release();
+  double* pows = t.reals();
   double* d = pows + NH;
 #pragma unroll
   for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k < NH) {
-      pows[k] = pv[i];
-      d[k] = log10(pv[i]);
-    }
-  }
-  __syncthreads();
-  int idx, kc;
-  nf_search<0>(d, nullptr, NH, sh, idx, kc);
-  nf_finish(pows, NH, kc, idx, fact, sh, r, noise, kc_out, idx_out);
-}
-
-// the same for any nbin in [16, 8192].  Dynamic LDS: nbin + 2 doubles (the
-// row, then pows and d in its place).
-constexpr int kNfGenKI = (8192 / 2 + 1 + kBlock - 1) / kBlock;
-
-__global__ __launch_bounds__(kBlock) void k_noise_fit_rows_gen(const double* __restrict__ in,
-                                                               double fact,
-                                                               double* __restrict__ noise,
-                                                               int* __restrict__ kc_out,
-                                                               int* __restrict__ idx_out,
-                                                               const double2* __restrict__ tw,
-                                                               int nbin) {
-  extern __shared__ __align__(16) unsigned char gsm[];
-  double* x = reinterpret_cast<double*>(gsm);
-  __shared__ NoiseFitShared sh;
-  const int r = blockIdx.x, NH = nbin / 2 + 1;
-  load_real_row(x, in + (size_t)r * nbin, nbin);
-  __syncthreads();
-  double pv[kNfGenKI];
-#pragma unroll
-  for (int i = 0; i < kNfGenKI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    pv[i] = k < NH ? cabs2(dft_bin(x, nbin, k, tw)) / (double)nbin : 0.0;
-  }
-  __syncthreads();
-  double* pows = x;
-  double* d = x + NH;
-#pragma unroll
-  for (int i = 0; i < kNfGenKI; ++i) {
     const int k = threadIdx.x + i * kBlock;
     if (k < NH) {
       pows[k] = pv[i];
@@ -326,17 +285,18 @@ __global__ __launch_bounds__(kBlock) void k_find_kc_rows(const double* __restric
   }
 }
 
-#define PPF_INST_NF(L)                                                                  \
-  template __global__ void k_noise_fit_rows<L>(const double*, double, double*, int*, int*, \
-                                               const double2*);
-PPF_INST_NF(5)
-PPF_INST_NF(6)
-PPF_INST_NF(7)
-PPF_INST_NF(8)
-PPF_INST_NF(9)
-PPF_INST_NF(10)
-PPF_INST_NF(11)
-PPF_INST_NF(12)
+#define PPF_INST_NF(R)                                                                  \
+  template __global__ void k_noise_fit_rows<R>(const double*, double, double*, int*, int*, \
+                                               const double2*, R);
+PPF_INST_NF(RowPow2<5>)
+PPF_INST_NF(RowPow2<6>)
+PPF_INST_NF(RowPow2<7>)
+PPF_INST_NF(RowPow2<8>)
+PPF_INST_NF(RowPow2<9>)
+PPF_INST_NF(RowPow2<10>)
+PPF_INST_NF(RowPow2<11>)
+PPF_INST_NF(RowPow2<12>)
+PPF_INST_NF(RowAny)
 template __global__ void k_find_kc_rows<0>(const double*, const double*, int, int*, int*);
 template __global__ void k_find_kc_rows<1>(const double*, const double*, int, int*, int*);
 

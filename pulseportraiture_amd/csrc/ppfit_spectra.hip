@@ -21,48 +21,34 @@ __global__ void k_twiddles(double2* tw, int nbin) {
   }
 }
 
-// Load a real row of 2N doubles as N packed complex values into LDS.
-template <int LOGN>
-__device__ __forceinline__ void load_row(double2* buf, const double* __restrict__ row) {
-  constexpr int N = 1 << LOGN;
-  const double2* r2 = reinterpret_cast<const double2*>(row);
-#pragma unroll
-  for (int c = 0; c < (N + kBlock - 1) / kBlock; ++c) {
-    const int j = threadIdx.x + c * kBlock;
-    if (j < N) buf[j] = r2[j];
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Template spectra: M[row][k] for k <= N (DC zeroed when zero_dc, F0_fact=0,
 // pplib.py:66), zero padding up to NHP, and p_n = sum_{k>=1} |M_k|^2.
 // ---------------------------------------------------------------------------
-template <int LOGN>
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_model_spec(const double* __restrict__ model,
                                                        double2* __restrict__ M,
                                                        double* __restrict__ pn, int NHP,
                                                        int zero_dc,
                                                        const double2* __restrict__ tw,
-                                                       double* __restrict__ M2) {
-  constexpr int N = 1 << LOGN;
-  __shared__ double2 buf[N];
+                                                       double* __restrict__ M2, Row row) {
+  __shared__ typename Row::template Lds<kLdsRow> sm;
   __shared__ double red[kWaves];
-  const int row = blockIdx.x;
-  load_row<LOGN>(buf, model + (size_t)row * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, NH = t.nh();
+  t.load(model + (size_t)r * t.nbin());
   double p = 0.0;
-  double2* out = M + (size_t)row * NHP;
+  double2* out = M + (size_t)r * NHP;
   for (int k = threadIdx.x; k < NHP; k += kBlock) {
     double2 x = cmk(0.0, 0.0);
-    if (k <= N) x = rfft_post<LOGN>(buf, k, tw);
+    if (k < NH) x = t.bin(k);
     if (k == 0 && zero_dc) x = cmk(0.0, 0.0);
-    if (k >= 1 && k <= N) p += cabs2(x);
+    if (k >= 1 && k < NH) p += cabs2(x);
     out[k] = x;
-    if (M2) M2[(size_t)row * NHP + k] = cabs2(x);  // |M_k|^2 for the scattering sweeps
+    if (M2) M2[(size_t)r * NHP + k] = cabs2(x);  // |M_k|^2 for the scattering sweeps
   }
   p = block_sum(p, red);
-  if (threadIdx.x == 0 && pn) pn[row] = p;
+  if (threadIdx.x == 0 && pn) pn[r] = p;
 }
 
 // ---------------------------------------------------------------------------
@@ -391,46 +377,35 @@ __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
 // fit_phase_shift on profiles: spectrum + noise in-kernel, then the shared
 // brute-force + Nelder-Mead search (ppfit_guess.hpp).
 // ---------------------------------------------------------------------------
-template <int LOGN>
-__global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a) {
-  constexpr int N = 1 << LOGN;
-  constexpr int NH = N + 1;
-  __shared__ double2 buf[N + 1];
-  __shared__ double2 rm[N + 1];
+template <class Row>
+__global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a, Row row) {
+  __shared__ typename Row::template Lds<kLdsRowSpec> sm;
   __shared__ GuessShared gs;
-  const int r = blockIdx.x;
-  const int tid = threadIdx.x;
-  load_row<LOGN>(buf, a.data + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, a.tw);
+  typename Row::Dev t(row, sm, a.tw);
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int nbin = t.nbin(), NH = t.nh();
+  double2* rm = t.spec;
+  t.load(a.data + (size_t)r * nbin);
   const int midx = a.model_idx ? a.model_idx[r] : 0;
   const double2* Mr = a.M + (size_t)midx * a.NHP;
   double pnoise = 0.0, dd = 0.0, pp = 0.0;
-  double2 xs[(NH + kBlock - 1) / kBlock];
-#pragma unroll
-  for (int i = 0; i < (NH + kBlock - 1) / kBlock; ++i) {
-    const int k = tid + i * kBlock;
-    if (k <= N) {
-      double2 x = rfft_post<LOGN>(buf, k, a.tw);
-      if (k >= a.kc) pnoise += cabs2(x);
-      if (k == 0) x = cmk(0.0, 0.0);
-      xs[i] = x;
-      dd += cabs2(x);
-      pp += cabs2(Mr[k]);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < (NH + kBlock - 1) / kBlock; ++i) {
-    const int k = tid + i * kBlock;
-    if (k <= N) rm[k] = cmulc(xs[i], Mr[k]);
-  }
+  typename Row::Own xs(rm);
+  t.for_bins([&](int i, int k) {
+    double2 x = t.bin(k);
+    if (k >= a.kc) pnoise += cabs2(x);
+    if (k == 0) x = cmk(0.0, 0.0);
+    xs.at(i, k) = x;
+    dd += cabs2(x);
+    pp += cabs2(Mr[k]);
+  });
+  t.release();
+  t.for_bins([&](int i, int k) { rm[k] = cmulc(xs.at(i, k), Mr[k]); });
   pnoise = block_sum(pnoise, gs.red);
   dd = block_sum(dd, gs.red);
   pp = block_sum(pp, gs.red);
   double noise = a.noise ? a.noise[r] : NAN;
-  if (isnan(noise)) noise = sqrt(pnoise / (double)(2 * N) / (double)(NH - a.kc));
-  const double err = noise * sqrt((double)N);  // sqrt(nbin / 2)
+  if (isnan(noise)) noise = sqrt(pnoise / (double)nbin / (double)(NH - a.kc));
+  const double err = noise * sqrt(0.5 * (double)nbin);
   const double ie2 = 1.0 / (err * err);
   guess_search(rm, NH, ie2, a.Ns, a.lo, a.hi, gs);
   if (tid == 0) {
@@ -462,7 +437,7 @@ __global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a) {
     o[2] = scale;
     o[3] = pow(p, -0.5);
     o[4] = pow(scale * scale * p, 0.5);
-    o[5] = (d - fmin * fmin / p) / (double)(2 * N - 2);
+    o[5] = (d - fmin * fmin / p) / (double)(nbin - 2);
   }
 }
 
@@ -470,230 +445,160 @@ __global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a) {
 // Row rotation: out = irfft(rfft(in) e^{2 pi i k phase}) (rotate_data),
 // optionally scattered: / (1 + 2 pi i k tau) (scattering_portrait_FT).
 // ---------------------------------------------------------------------------
-// epi(j, v): the value stored at complex sample j (bins 2j, 2j + 1), given
-// the transform's v -- a fused epilogue (k_synth adds its noise there)
-struct C2rPlain {
-  __device__ double2 operator()(int, double2 v) const { return v; }
-};
-// The transform alone: buf[j] (j in [0, N)) is left holding N times the sample
-// pair (2j, 2j + 1); the caller synchronises nothing more before reading its
-// own j = tid + i kBlock.
-template <int LOGN>
-__device__ void c2r_in_lds(double2* buf, double2 (&xs)[((1 << LOGN) + kBlock) / kBlock + 1],
-                           const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  const int tid = threadIdx.x;
-  // stage X_k (k in [0, N]) in LDS, then form Z_k for k in [0, N)
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = tid + i * kBlock;
-    if (k <= N) {
-      double2 x = xs[i];
-      if (k == 0 || k == N) x.y = 0.0;
-      buf[k] = x;
-    }
-  }
-  __syncthreads();
-  double2 z[KI];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = tid + i * kBlock;
-    if (k < N) z[i] = irfft_pre<LOGN>(buf[k], buf[N - k], k, tw);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = tid + i * kBlock;
-    if (k < N) buf[k] = z[i];
-  }
-  __syncthreads();
-  lds_fft<LOGN, true>(buf, tw);
-}
-
-template <int LOGN, typename Epi = C2rPlain>
-__device__ void c2r_from_spectrum(double2* buf, double2 (&xs)[((1 << LOGN) + kBlock) / kBlock + 1],
-                                  const double2* __restrict__ tw, double* __restrict__ out,
-                                  Epi epi = Epi()) {
-  constexpr int N = 1 << LOGN;
-  c2r_in_lds<LOGN>(buf, xs, tw);
-  const double inv = 1.0 / (double)N;
-  double2* o2 = reinterpret_cast<double2*>(out);
-  for (int j = threadIdx.x; j < N; j += kBlock) o2[j] = epi(j, cscale(buf[j], inv));
-}
-
-template <int LOGN>
 // in == out is supported (ppf_rotate_rows in place, engine.rotate_rows):
 // each workgroup loads its whole row into LDS and synchronises before any
 // store, so in and out are deliberately not __restrict__.
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_rotate_rows(const double* in,
                                                         const double* __restrict__ phase,
                                                         const double* __restrict__ tau,
                                                         double* out,
-                                                        const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
-  const int r = blockIdx.x;
-  load_row<LOGN>(buf, in + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+                                                        const double2* __restrict__ tw, Row row) {
+  __shared__ typename Row::template Lds<kLdsRowInv> sm;
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, nbin = t.nbin();
+  t.load(in + (size_t)r * nbin);
   const double ph = phase ? phase[r] : 0.0;
-  double2 xs[(N + kBlock) / kBlock + 1];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) {
-      xs[i] = rfft_post<LOGN>(buf, k, tw);
-      if (phase) xs[i] = cmul(xs[i], turn_phasor((double)k, ph));
-    }
-  }
+  typename Row::Own xs(t.spec);
+  t.for_bins([&](int i, int k) {
+    double2 v = t.bin(k);
+    if (phase) v = cmul(v, turn_phasor((double)k, ph));
+    xs.at(i, k) = v;
+  });
   const double t2 = tau ? 2.0 * M_PI * tau[r] : 0.0;
-  if (t2 != 0.0) {  // scattering_portrait_FT: x / (1 + 2 pi i k tau)
-#pragma unroll
-    for (int i = 0; i < KI; ++i) {
-      const int k = threadIdx.x + i * kBlock;
-      const double w = t2 * (double)k, d = 1.0 / fma(w, w, 1.0);
-      if (k <= N) xs[i] = cmk(fma(xs[i].y, w, xs[i].x) * d, fma(-xs[i].x, w, xs[i].y) * d);
-    }
-  }
-  __syncthreads();
-  c2r_from_spectrum<LOGN>(buf, xs, tw, out + (size_t)r * 2 * N);
+  if (t2 != 0.0)  // scattering_portrait_FT: x / (1 + 2 pi i k tau)
+    t.for_bins([&](int i, int k) { xs.at(i, k) = scat_div(xs.at(i, k), t2 * (double)k); });
+  if constexpr (Row::kFft) __syncthreads();  // every bin is taken: the buffer is the inverse's
+  t.inverse(xs, out + (size_t)r * nbin);
 }
 
-template <int LOGN>
+// out[r] = irfft(spec[r], n = nbin)
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_irfft_rows(const double2* __restrict__ spec,
                                                        double* __restrict__ out,
-                                                       const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
-  const int r = blockIdx.x;
-  double2 xs[(N + kBlock) / kBlock + 1];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) xs[i] = spec[(size_t)r * (N + 1) + k];
-  }
-  c2r_from_spectrum<LOGN>(buf, xs, tw, out + (size_t)r * 2 * N);
+                                                       const double2* __restrict__ tw, Row row) {
+  __shared__ typename Row::template Lds<kLdsSpec> sm;
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, NH = t.nh();
+  typename Row::Own xs(t.spec);
+  t.for_bins([&](int i, int k) { xs.at(i, k) = spec[(size_t)r * NH + k]; });
+  t.inverse(xs, out + (size_t)r * t.nbin());
 }
 
-// spec[r][k] = rfft(in[r])[k], k in [0, N] (numpy rfft layout; nothing zeroed)
-template <int LOGN>
+// spec[r][k] = rfft(in[r])[k], k <= nbin/2 (numpy rfft layout; nothing zeroed)
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_rfft_rows(const double* __restrict__ in,
                                                       double2* __restrict__ spec,
-                                                      const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  __shared__ double2 buf[N];
-  const int r = blockIdx.x;
-  load_row<LOGN>(buf, in + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
-  for (int k = threadIdx.x; k <= N; k += kBlock)
-    spec[(size_t)r * (N + 1) + k] = rfft_post<LOGN>(buf, k, tw);
+                                                      const double2* __restrict__ tw, Row row) {
+  __shared__ typename Row::template Lds<kLdsRow> sm;
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, NH = t.nh();
+  t.load(in + (size_t)r * t.nbin());
+  for (int k = threadIdx.x; k < NH; k += kBlock) spec[(size_t)r * NH + k] = t.bin(k);
 }
 
-template <int LOGN>
+// get_noise_PS per row (pplib.py:2227-2253)
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_noise_rows(const double* __restrict__ in,
                                                        double* __restrict__ out, int kc,
-                                                       const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  __shared__ double2 buf[N];
+                                                       const double2* __restrict__ tw, Row row) {
+  __shared__ typename Row::template Lds<kLdsRow> sm;
   __shared__ double red[kWaves];
-  const int r = blockIdx.x;
-  load_row<LOGN>(buf, in + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, nbin = t.nbin(), NH = t.nh();
+  t.load(in + (size_t)r * nbin);
   double p = 0.0;
-  for (int k = kc + threadIdx.x; k <= N; k += kBlock) p += cabs2(rfft_post<LOGN>(buf, k, tw));
+  for (int k = kc + threadIdx.x; k < NH; k += kBlock) p += cabs2(t.bin(k));
   p = block_sum(p, red);
-  if (threadIdx.x == 0) out[r] = sqrt(p / (double)(2 * N) / (double)(N + 1 - kc));
+  if (threadIdx.x == 0) out[r] = sqrt(p / (double)nbin / (double)(NH - kc));
 }
 
 // ---------------------------------------------------------------------------
 // Synthetic portraits: data[s][n] = irfft(Mfull_n e^{2 pi i k phase[s][n]})
 //                                   + sigma * Philox normals.
 // ---------------------------------------------------------------------------
-template <int LOGN>
+// Sample pair j of channel n, subint gs: counter (j, n, gs); at odd nbin the
+// last sample takes the first normal of its pair (synth.noise_block's layout).
+struct SynthEpi {
+  double sigma;
+  uint64_t seed, gs;
+  int n;
+  __device__ __forceinline__ bool active() const { return sigma != 0.0; }
+  // v0: the transform's value (RowAny: read from the stored row, after the normals)
+  template <class V>
+  __device__ __forceinline__ double2 operator()(int j, V v0) const {
+    if (sigma == 0.0) return v0;
+    u32x4 ctr;
+    ctr.v[0] = (uint32_t)j;
+    ctr.v[1] = (uint32_t)n;
+    ctr.v[2] = (uint32_t)gs;
+    ctr.v[3] = (uint32_t)(gs >> 32);
+    const double2 z = philox_normal2(ctr, seed);
+    const double2 v = v0;
+    return cmk(fma(sigma, z.x, v.x), fma(sigma, z.y, v.y));
+  }
+};
+
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_synth(const double2* __restrict__ Mfull,
                                                   const double* __restrict__ phase,
                                                   double* __restrict__ data, int nchan,
                                                   int NHP, double sigma, uint64_t seed,
                                                   int64_t sub0,
-                                                  const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
+                                                  const double2* __restrict__ tw, Row rw) {
+  __shared__ typename Row::template Lds<kLdsSpec> sm;
+  typename Row::Dev t(rw, sm, tw);
   const int row = blockIdx.x;  // s * nchan + n
   const int n = row % nchan;
   const int64_t s = row / nchan;
   const double ph = phase[row];
-  double2 xs[(N + kBlock) / kBlock + 1];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) xs[i] = cmul(Mfull[(size_t)n * NHP + k], turn_phasor((double)k, ph));
-  }
-  double* out = data + (size_t)row * 2 * N;
-  // the noise joins each sample pair as it is stored (one pass over the row)
-  const uint64_t gs = (uint64_t)(s + sub0);
-  c2r_from_spectrum<LOGN>(buf, xs, tw, out, [&](int j, double2 v) {
-    if (sigma != 0.0) {
-      u32x4 ctr;
-      ctr.v[0] = (uint32_t)j;
-      ctr.v[1] = (uint32_t)n;
-      ctr.v[2] = (uint32_t)gs;
-      ctr.v[3] = (uint32_t)(gs >> 32);
-      const double2 z = philox_normal2(ctr, seed);
-      v.x = fma(sigma, z.x, v.x);
-      v.y = fma(sigma, z.y, v.y);
-    }
-    return v;
+  typename Row::Own xs(t.spec);
+  t.for_bins([&](int i, int k) {
+    xs.at(i, k) = cmul(Mfull[(size_t)n * NHP + k], turn_phasor((double)k, ph));
   });
+  // the noise joins each sample pair as it is stored (RowPow2: in the same pass)
+  t.inverse(xs, data + (size_t)row * t.nbin(), SynthEpi{sigma, seed, (uint64_t)(s + sub0), n});
 }
 
 // ---------------------------------------------------------------------------
 // ppalign weighted rotate-and-sum in the Fourier domain (ppalign.py:202-208):
-// partial[p][n][k] = sum_{s in slice p} w[s][n] rfft(data[s][n])_k e^{2 pi i k ph[s][n]}
+// partial[p][n][k] = sum_{s in slice p} w[s][n] rfft(data[s][n])_k e^{2 pi i k ph[s][n]},
+// each k summed by one thread in subint order: in registers (RowPow2) or in
+// its cell of the partial spectrum (RowAny).
 // ---------------------------------------------------------------------------
-template <int LOGN>
+// acc_k += w D_k e^{2 pi i k ph} over the thread's bins of the loaded row
+template <class Dev, class Own>
+__device__ __forceinline__ void rot_add(Dev& t, Own& acc, double ph, double w) {
+  t.for_bins([&](int i, int k) {
+    acc.at(i, k) = cadd(acc.at(i, k), cscale(cmul(t.bin(k), turn_phasor((double)k, ph)), w));
+  });
+}
+
+template <class Row>
 __global__ __launch_bounds__(kBlock) void k_rot_accum(const double* __restrict__ data,
                                                       const double* __restrict__ phase,
                                                       const double* __restrict__ weight,
                                                       double2* __restrict__ partial, int nsub,
                                                       int nchan, int nsplit,
-                                                      const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N];
+                                                      const double2* __restrict__ tw, Row rw) {
+  __shared__ typename Row::template Lds<kLdsRow> sm;
+  typename Row::Dev t(rw, sm, tw);
   const int n = blockIdx.x % nchan;
   const int p = blockIdx.x / nchan;
   const int per = (nsub + nsplit - 1) / nsplit;
   const int s0 = p * per, s1 = min(nsub, s0 + per);
-  double2 acc[KI];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) acc[i] = cmk(0.0, 0.0);
+  double2* out = partial + ((size_t)p * nchan + n) * t.nh();
+  typename Row::Own acc(out);
+  t.for_bins([&](int i, int k) { acc.at(i, k) = cmk(0.0, 0.0); });
   for (int s = s0; s < s1; ++s) {
     const size_t row = (size_t)s * nchan + n;
     const double w = weight[row];
     if (w == 0.0) continue;  // uniform per block
-    load_row<LOGN>(buf, data + row * 2 * N);
-    __syncthreads();
-    lds_fft<LOGN, false>(buf, tw);
-    const double ph = phase[row];
-#pragma unroll
-    for (int i = 0; i < KI; ++i) {
-      const int k = threadIdx.x + i * kBlock;
-      if (k <= N)
-        acc[i] = cadd(acc[i], cscale(cmul(rfft_post<LOGN>(buf, k, tw), turn_phasor((double)k, ph)), w));
-    }
-    __syncthreads();
+    t.load(data + row * t.nbin());
+    rot_add(t, acc, phase[row], w);
+    t.release();
   }
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) partial[((size_t)p * nchan + n) * (N + 1) + k] = acc[i];
-  }
+  if constexpr (Row::kFft) t.for_bins([&](int i, int k) { out[k] = acc.at(i, k); });
 }
 
 // The same sum for nbin = 2048 (ppalign at config 5).  Workgroup (n, p)
@@ -882,70 +787,59 @@ __global__ void k_accum_reduce(const double2* __restrict__ partial, double2* __r
 //   out[r] = (Re(R_0)^2 + Re(R_N)^2 + 2 sum_{0<k<N} |R_k|^2) / nbin / errs[r]^2 / dof
 // One workgroup per row; both FFTs in LDS, nothing materialised in HBM.
 // ---------------------------------------------------------------------------
-template <int LOGN>
-__global__ __launch_bounds__(kBlock) void k_resid_chi2(ResidArgs a, const double2* __restrict__ tw) {
-  constexpr int N = 1 << LOGN;
-  constexpr int KI = (N + 1 + kBlock - 1) / kBlock;
-  __shared__ double2 buf[N + 1];
+template <class Row>
+__global__ __launch_bounds__(kBlock) void k_resid_chi2(ResidArgs a, const double2* __restrict__ tw,
+                                                       Row row) {
+  __shared__ typename Row::template Lds<kLdsRowInv> sm;
   __shared__ double red[kWaves];
-  const int r = blockIdx.x;
-  load_row<LOGN>(buf, a.data + (size_t)r * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+  typename Row::Dev t(row, sm, tw);
+  const int r = blockIdx.x, nbin = t.nbin();
+  t.load(a.data + (size_t)r * nbin);
   const double ph = a.phase ? a.phase[r] : 0.0;
-  double2 xs[(N + kBlock) / kBlock + 1];
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) xs[i] = cmul(rfft_post<LOGN>(buf, k, tw), turn_phasor((double)k, ph));
-  }
-  __syncthreads();
-  load_row<LOGN>(buf, a.model + (size_t)(a.model_row ? a.model_row[r] : r) * 2 * N);
-  __syncthreads();
-  lds_fft<LOGN, false>(buf, tw);
+  typename Row::Own xs(t.spec);
+  t.for_bins([&](int i, int k) { xs.at(i, k) = cmul(t.bin(k), turn_phasor((double)k, ph)); });
+  t.release();
+  t.load(a.model + (size_t)(a.model_row ? a.model_row[r] : r) * nbin);
   const double sc = a.scale[r];
   const double t2 = a.tau ? 2.0 * M_PI * a.tau[r] : 0.0;
   double acc = 0.0;
-#pragma unroll
-  for (int i = 0; i < KI; ++i) {
-    const int k = threadIdx.x + i * kBlock;
-    if (k <= N) {
-      double2 m = rfft_post<LOGN>(buf, k, tw);
-      if (t2 != 0.0) {  // m / (1 + i w),  w = 2 pi k tau
-        const double w = t2 * (double)k, d = 1.0 / fma(w, w, 1.0);
-        m = cmk(fma(m.y, w, m.x) * d, fma(-m.x, w, m.y) * d);
-      }
-      const double2 q = cmk(fma(-sc, m.x, xs[i].x), fma(-sc, m.y, xs[i].y));
-      // irfft keeps only the real part of the DC and Nyquist terms
-      acc += (k == 0 || k == N) ? q.x * q.x : 2.0 * cabs2(q);
-    }
-  }
+  t.for_bins([&](int i, int k) {
+    double2 m = t.bin(k);
+    if (t2 != 0.0) m = scat_div(m, t2 * (double)k);  // m / (1 + i w),  w = 2 pi k tau
+    const double2 d = xs.at(i, k);
+    const double2 q = cmk(fma(-sc, m.x, d.x), fma(-sc, m.y, d.y));
+    // irfft keeps only the real part of the DC and (even nbin) Nyquist terms
+    const bool real_only = k == 0 || (!(nbin & 1) && k == nbin / 2);
+    acc += real_only ? q.x * q.x : 2.0 * cabs2(q);
+  });
   acc = block_sum(acc, red);
   if (threadIdx.x == 0) {
     const double e = a.errs[r];
-    a.out[r] = acc / (double)(2 * N) / (e * e) / a.dof;
+    a.out[r] = acc / (double)nbin / (e * e) / a.dof;
   }
 }
 
 // ---------------------------------------------------------------------------
-// explicit instantiations (nbin = 64 ... 8192  <=>  LOGN = 5 ... 12)
+// explicit instantiations (nbin = 64 ... 8192  <=>  LOGN = 5 ... 12, and any nbin)
 // ---------------------------------------------------------------------------
+#define PPF_INST_ROW(R)                                                                      \
+  template __global__ void k_model_spec<R>(const double*, double2*, double*, int, int,       \
+                                           const double2*, double*, R);                      \
+  template __global__ void k_phase_shift<R>(PhaseShiftArgs, R);                              \
+  template __global__ void k_rotate_rows<R>(const double*, const double*, const double*,     \
+                                            double*, const double2*, R);                     \
+  template __global__ void k_resid_chi2<R>(ResidArgs, const double2*, R);                    \
+  template __global__ void k_irfft_rows<R>(const double2*, double*, const double2*, R);      \
+  template __global__ void k_rfft_rows<R>(const double*, double2*, const double2*, R);       \
+  template __global__ void k_noise_rows<R>(const double*, double*, int, const double2*, R);  \
+  template __global__ void k_synth<R>(const double2*, const double*, double*, int, int,      \
+                                      double, uint64_t, int64_t, const double2*, R);         \
+  template __global__ void k_rot_accum<R>(const double*, const double*, const double*,       \
+                                          double2*, int, int, int, const double2*, R);
 #define PPF_INST(L)                                                                          \
-  template __global__ void k_model_spec<L>(const double*, double2*, double*, int, int,       \
-                                           const double2*, double*);                         \
   template __global__ void k_data_xspec<L, false>(SpecArgs);                                 \
   template __global__ void k_data_xspec<L, true>(SpecArgs);                                  \
-  template __global__ void k_phase_shift<L>(PhaseShiftArgs);                                 \
-  template __global__ void k_rotate_rows<L>(const double*, const double*, const double*,     \
-                                            double*, const double2*);                        \
-  template __global__ void k_resid_chi2<L>(ResidArgs, const double2*);                       \
-  template __global__ void k_irfft_rows<L>(const double2*, double*, const double2*);        \
-  template __global__ void k_rfft_rows<L>(const double*, double2*, const double2*);         \
-  template __global__ void k_noise_rows<L>(const double*, double*, int, const double2*);    \
-  template __global__ void k_synth<L>(const double2*, const double*, double*, int, int,      \
-                                      double, uint64_t, int64_t, const double2*);            \
-  template __global__ void k_rot_accum<L>(const double*, const double*, const double*,       \
-                                          double2*, int, int, int, const double2*);
+  PPF_INST_ROW(RowPow2<L>)
 PPF_INST(5)
 PPF_INST(6)
 PPF_INST(7)
@@ -954,5 +848,6 @@ PPF_INST(9)
 PPF_INST(10)
 PPF_INST(11)
 PPF_INST(12)
+PPF_INST_ROW(RowAny)
 
 }  // namespace ppf

@@ -161,7 +161,7 @@ def gen_gaussian_portrait(model_code, params, scattering_index, phases, freqs, n
     port = np.array([gen_gaussian_profile(gp[i], nbin) for i in range(nchan)])
     if tau != 0.0:
         taus = scattering_times(float(tau) / nbin, scattering_index, freqs, nu_ref)
-        # n=nbin as the device's k_rotate_rows_gen (pplib.py:921 has no n=
+        # n=nbin as the device's k_rotate_rows<RowAny> (pplib.py:921 has no n=
         # and returns nbin - 1 bins at odd nbin); the same for even nbin
         port = np.fft.irfft(scattering_portrait_FT(taus, nbin) *
                             np.fft.rfft(port, axis=-1), n=nbin, axis=-1)

@@ -1,4 +1,4 @@
-"""nbin that are not powers of two (ppfit_generic.hip).
+"""nbin that are not powers of two (ppfit_generic.hip, RowAny of ppfit_rowfft.hpp).
 
 The reference transforms with numpy's rfft / irfft of any length
 (pptoaslib.py:976-978, pplib.py:2338-2426); the library's FFT kernels are
@@ -58,7 +58,7 @@ def test_rotate_rows_generic(eng, nbin):
 @pytest.mark.parametrize("tau", [0.0, 4.0])
 def test_gaussian_portraits_generic(eng, nbin, tau):
     """The .gmodel template on the device (k_gauss_port, and the scattering
-    rotation through k_rotate_rows_gen) against gen_gaussian_portrait's numpy
+    rotation through k_rotate_rows<RowAny>) against gen_gaussian_portrait's numpy
     form, at 1e-12 of the row scale.  Odd nbin with scattering: the
     reference's irfft has no n= (pplib.py:921) and returns nbin - 1 bins, a
     template that no longer matches its data; the device keeps nbin bins,
@@ -202,11 +202,19 @@ def test_get_toas_generic_nbin(tmp_path):
     assert np.all(np.abs(dms - (w.DM0 + w.dDM)) < 6 * np.asarray(gt.DM_errs[0]))
 
 
-@pytest.mark.parametrize("nbin", [1000, 999, 8191])
+# Both transform families under the same assertions: direct sums below 64
+# bins and at every length that is no power of two, the LDS FFT from 64 up.
+# 16: the smallest nbin; 33: odd, less than one block; 64 and 128: the
+# smallest FFT instantiations (fewer bins than threads); 512: nbin/2 + 1 =
+# kBlock + 1, the first shape where a thread owns two bins; 8192: the largest.
+ROW_NBINS = [16, 33, 64, 128, 512, 999, 1000, 8191, 8192]
+
+
+@pytest.mark.parametrize("nbin", ROW_NBINS)
 def test_row_entry_points_generic(eng, nbin):
     """get_noise_PS, irfft, fit_phase_shift (ppalign / pplib FFTFIT), the
-    zapping residual chi2 and ppalign's rotate-and-sum at a generic nbin,
-    against numpy / the oracle."""
+    zapping residual chi2 and ppalign's rotate-and-sum, against numpy / the
+    oracle, at lengths of both transform families."""
     import torch
     w = synth.make_workload(1, 6, nbin, seed=730 + nbin)
     data = synth.workload_data_host(w)[0]

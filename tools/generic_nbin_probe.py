@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fit time at a generic nbin against the neighbouring power of two (same
-subints x channels, phase + DM, guess): where the direct-sum data pass
-(k_data_xspec_gen, O(nbin^2) per row) puts the generic-length path.
+subints x channels, phase + DM, guess): where the O(nbin^2) data pass
+(k_dft_rows_mfma + k_data_post_gen, template spectra from
+k_model_spec<RowAny>) puts the generic-length path.
 
   generic_nbin_probe.py [NSUB] [NCHAN]
 """
