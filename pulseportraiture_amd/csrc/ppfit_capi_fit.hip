@@ -146,7 +146,9 @@ int stage_moments(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa) {
 int stage_taylor(ppf_ctx* ctx, hipStream_t st, int n, const FitArgs& fa, const FitLaunch& L) {
   const bool mom = ctx->opt[PPF_OPT_FUSE_MOMENTS] != 0;
   const dim3 g(n), b(kBlock);
-  const size_t lds = L.lds_taylor;
+  // the fused moment pass over X stages through the same dynamic LDS first
+  const bool stage = PPF_MOM_STAGE && mom && !fa.Dsp;
+  const size_t lds = stage ? std::max(L.lds_taylor, kWaves * kMomStageBytes) : L.lds_taylor;
   return timed_on(ctx, PPF_K_FIT_TAYLOR, st, [&] {
     WIDE_SWITCH(L.wide, {
       if (fa.Dsp) {

@@ -19,6 +19,12 @@
 // row's load inside the register FFT, right after stage A (A/B knob)
 #define PPF_EARLY_ROW 1
 #endif
+#ifndef PPF_MOM_STAGE
+// k_fit_taylor's fused first moment pass over X: 1 = coalesced row loads
+// staged through LDS one block ahead (moment_tile16_staged), 0 = the direct
+// per-lane loads of moment_tile16, k_moments' loop (A/B knob)
+#define PPF_MOM_STAGE 1
+#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>

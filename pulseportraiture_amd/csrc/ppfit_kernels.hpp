@@ -96,6 +96,11 @@ constexpr int kMTerm = kMT - 2;
 // limit is the same three blocks): all kMT up to 128 channels, 16 at 256
 constexpr size_t kLdsPerCU = 160 * 1024;
 constexpr int kTaylorBlocksPerCU = 3;
+// k_fit_taylor's fused moment pass over X stages blocks of 16 channels x 16
+// harmonics through LDS, one 4 KB buffer per wave at the start of the
+// kernel's dynamic LDS; the channel tables and the T copy take the same
+// bytes once the pass has ended (the launch gets the larger of the two)
+constexpr size_t kMomStageBytes = 16 * 16 * 16;
 constexpr double kTaylorY = 3.0;
 
 // Per-subint solver state handed from the guess kernels to the solver and on

@@ -72,8 +72,10 @@ __device__ __forceinline__ void rs_swap(const double* v, double* out) {
 // moments (kernels.hpp), Re T_m for even m and Im T_m for odd m, and nothing
 // else -- two MFMAs per step.  Lane l supplies harmonic 4 s + (l >> 4) of
 // channel l & 15 to B and v^(2 (l & 15)), v^(2 (l & 15) + 1) of that harmonic
-// to A (v is exact when N is a power of two).  X rows stream through
-// registers U steps ahead of the MFMAs.  All kMT moments are kept (cnt =
+// to A (v is exact when N is a power of two).  k_moments and the recentring
+// load each lane's own cells (moment_tile16 / moment_tile8); k_fit_taylor's
+// fused first pass fetches X by rows through LDS, one block ahead of the
+// MFMAs (moment_tile16_staged).  All kMT moments are kept (cnt =
 // kMT): the truncation bound then holds for any spectrum.
 // ---------------------------------------------------------------------------
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -136,9 +138,12 @@ __global__ void k_vpow(double2* vp, int nbin, int rows) {
 // separate accumulators (independent chains).
 // A lane rotates its own element and feeds it straight to the matrix core:
 // no cross-lane trade, no select.  Its two phasor chains (even / odd steps)
-// restart from turn_phasor every kMomReseedSteps steps.  The next block's X and power rows
-// stream into each step's registers as soon as its MFMAs have issued, so U
-// steps of loads stay in flight with one register set.
+// restart from turn_phasor every kMomReseedSteps steps.  Each step's registers are
+// reloaded with the next block's X and power rows after its MFMAs; the
+// compiler gathers those loads at the top of the next block and waits for
+// them there, so nothing is in flight across the MFMAs (the staged tile
+// below is the one that loads ahead).  One lane's loads of a step lie in 16
+// different rows: 64 requests of 16 B per load instruction.
 // DSP (data-spectrum cache, a.Dsp): the lane loads D_k and M_k instead and
 // forms X_k = D_k conj(M_k) (0 at k = 0) -- k_data_xspec's arithmetic on the
 // same operands, so the same X bit for bit.
@@ -217,6 +222,106 @@ __device__ __forceinline__ void moment_tile16(const FitArgs& a, int c, int slot,
   // D[row i = (l >> 4) + 4 r][col = channel l & 15]: moments 2 i and 2 i + 1
   if (ok) {
     double2* Tn = reinterpret_cast<double2*>(a.T + (((size_t)c * 2 + slot) * a.nchan + n) * kMT);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Tn[kk + 4 * r] = cmk(d0[r], g0[r]);
+  }
+}
+
+// moment_tile16<4, false> with the X loads coalesced and one block ahead
+// (k_fit_taylor's fused pass; n0 = the tile's first channel, n = n0 + col).
+// moment_tile16's lane reads 16 B of its own channel's row, so one load
+// instruction touches 16 rows; here a block of 16 harmonics x 16 channels (the
+// data of 4 steps) is fetched by rows -- load j of lane (kk, col) takes
+// harmonic 16 b + col of channel n0 + 4 j + kk, so every 16-lane group reads
+// 256 contiguous bytes (rows are 256-B aligned and NHP = 16 nblk: a block
+// never leaves its row) -- written to the wave's own 4 KB of LDS and read back
+// in the B layout, lane (kk, col) taking [channel col][harmonic 4 t + kk] for
+// step t.  Cell [ch][h] lives at 16-B slot 16 ch + (h ^ ch): each lane group
+// of ds_read_b128 (16 channels, two values of kk) and each 8-lane group of
+// ds_write_b128 (8 harmonics of a channel) covers distinct banks.
+// Block b + 1's loads are issued before block b's first MFMA, into the
+// registers that block b has just left for LDS, and waited for after its
+// last; the power rows roll as in moment_tile16.  A wave's LDS operations
+// complete in order and no other wave touches its buffer: no barrier.
+// Every MFMA sees moment_tile16's operands in its order: the same T bit for
+// bit.  Masked channels and channels past nchan (row clamped) are loaded and
+// zeroed at use, as there.
+__device__ __forceinline__ void moment_tile16_staged(const FitArgs& a, int c, int n0, int n,
+                                                     bool ok, double phic, double2* buf) {
+  static_assert(kMT == 32, "two 16-row MFMA tiles");
+  constexpr int U = 4;
+  static_assert(kMomStageBytes == 16 * 4 * U * sizeof(double2), "one block of U steps");
+  static_assert(kMomReseedSteps % U == 0, "re-seeds fall on block starts");
+  const int lane = threadIdx.x & 63;
+  const int N = a.nbin / 2;
+  const int nblk = (N + 1 + 15) / 16;  // blocks of U 4-harmonic steps
+  const int col = lane & 15, kk = lane >> 4;
+  const double2* __restrict__ Xc = a.X + (size_t)c * a.nchan * a.NHP;
+  unsigned goff[U];
+  int wr[U], rd[U];  // X cell of load j; its LDS slot; step t's LDS slot
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+    const int ch = 4 * j + kk;
+    goff[j] = (unsigned)min(n0 + ch, a.nchan - 1) * (unsigned)a.NHP + (unsigned)col;
+    wr[j] = 16 * ch + (col ^ ch);
+    rd[j] = 16 * col + ((4 * j + kk) ^ col);
+  }
+  const double2* __restrict__ vp = a.vpow + (size_t)kk * 16 + col;
+  const double2 s8 = turn_phasor(8.0, phic);
+  f64x4 d0 = {0.0, 0.0, 0.0, 0.0}, d2 = d0;
+  f64x4 g0 = d0, g2 = d0;
+  double2 xs[U], pb[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) xs[j] = xload(Xc + goff[j]);
+#pragma unroll
+  for (int t = 0; t < U; ++t) pb[t] = vp[(size_t)t * 64];
+  double2 e0 = cmk(1.0, 0.0), e1 = e0;
+  for (int b = 0; b < nblk; ++b) {
+    if ((b * U) % kMomReseedSteps == 0) {
+      e0 = turn_phasor((double)(4 * (b * U) + kk), phic);
+      e1 = turn_phasor((double)(4 * (b * U + 1) + kk), phic);
+    }
+    // block b to LDS (the previous block's reads have returned: in order)
+#pragma unroll
+    for (int j = 0; j < U; ++j) buf[wr[j]] = xs[j];
+    // block b + 1 on its way (after the last block: that block once more)
+    const unsigned bn = 16u * (unsigned)min(b + 1, nblk - 1);
+#pragma unroll
+    for (int j = 0; j < U; ++j) xs[j] = xload(Xc + goff[j] + bn);
+    __builtin_amdgcn_sched_barrier(0);
+    double2 xr[U];
+#pragma unroll
+    for (int t = 0; t < U; ++t) xr[t] = buf[rd[t]];
+    // (keeps the compiler from moving a read under its select's condition)
+    asm volatile("" : "+v"(xr[0].x), "+v"(xr[0].y), "+v"(xr[1].x), "+v"(xr[1].y),
+                      "+v"(xr[2].x), "+v"(xr[2].y), "+v"(xr[3].x), "+v"(xr[3].y));
+#pragma unroll
+    for (int t = 0; t < U; ++t) {
+      const bool on = ok & (4 * (b * U + t) + kk <= N);
+      xr[t] = cmk(on ? xr[t].x : 0.0, on ? xr[t].y : 0.0);
+    }
+#pragma unroll
+    for (int u = 0; u < U / 2; ++u) {
+      const double2 W0 = cmul(xr[2 * u], e0);
+      const double2 W1 = cmul(xr[2 * u + 1], e1);
+      const double2 p0 = pb[2 * u], p1 = pb[2 * u + 1];
+      d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(p0.x, W0.x, d0, 0, 0, 0);
+      g0 = __builtin_amdgcn_mfma_f64_16x16x4f64(p0.y, W0.y, g0, 0, 0, 0);
+      d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(p1.x, W1.x, d2, 0, 0, 0);
+      g2 = __builtin_amdgcn_mfma_f64_16x16x4f64(p1.y, W1.y, g2, 0, 0, 0);
+      e0 = cmul(e0, s8);
+      e1 = cmul(e1, s8);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int t = 2 * u + h;
+        pb[t] = vp[(size_t)((b + 1) * U + t) * 64];
+      }
+    }
+  }
+  d0 += d2;
+  g0 += g2;
+  if (ok) {
+    double2* Tn = reinterpret_cast<double2*>(a.T + ((size_t)c * 2 * a.nchan + n) * kMT);
 #pragma unroll
     for (int r = 0; r < 4; ++r) Tn[kk + 4 * r] = cmk(d0[r], g0[r]);
   }
@@ -426,7 +531,11 @@ __global__ __launch_bounds__(kBlock, 3) void k_fit_taylor(FitArgs a) {
       const bool ok = n < a.nchan && (!a.mask || a.mask[(size_t)s * a.nchan + n]);
       const double phic =
           ok ? phase_frac(st0.xc[0], a.freqs[(size_t)s * a.nchan + n], st0.refs, a.P[s]) : 0.0;
-      moment_tile16<DSP ? PPF_DSP_U : PPF_MOM_U, DSP>(a, c, 0, n, ok, phic);
+      if constexpr (!DSP && PPF_MOM_STAGE)
+        moment_tile16_staged(a, c, 16 * t, n, ok, phic,
+                             reinterpret_cast<double2*>(dyn + (size_t)w * kMomStageBytes));
+      else
+        moment_tile16<DSP ? PPF_DSP_U : PPF_MOM_U, DSP>(a, c, 0, n, ok, phic);
     }
     // T slot 0 is read back below by other waves of this workgroup
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
