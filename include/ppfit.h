@@ -97,7 +97,10 @@
  *    (PPF_SPEC_*, ppf_spec_nhp, ppf_rotate_accumulate_spec) and
  *    ppf_synth_portraits, ppf_fake_subints and ppf_pack_subints: every
  *    entry point takes any nbin in [16, 8192]
- *    (powers of two below 64 take the generic kernels too).
+ *    (powers of two below 64 take the generic kernels too).  Of those
+ *    lengths the even ones with nbin / 2 = 2^a 3^b 5^c take a mixed-radix
+ *    FFT in the row entry points and the fit's data pass instead
+ *    (ppf_row_transform, PPF_OPT_ROW_FFT).
  *  - Channel counts: up to PPF_LDS_NCHAN a fit workgroup keeps its subint's
  *    per-channel tables (frequencies, weights, dispersion derivatives, the
  *    fitted-channel list) in LDS; above it (or under PPF_OPT_HBM_TABLES) the
@@ -184,7 +187,17 @@ int ppf_set_pipeline(ppf_ctx* ctx, int32_t pieces);
  *                        count (default 0: only above PPF_LDS_NCHAN).
  *   PPF_OPT_POST_WAVE    1: the single-wave post-fit kernel (k_post_w) takes
  *                        the phase-family fits it covers (default); 0: every
- *                        post-fit in k_post.                                */
+ *                        post-fit in k_post.
+ * One option chooses between two implementations of the same transform, so
+ * its two settings agree to rounding (1e-12 of a row's scale), not bitwise:
+ *   PPF_OPT_ROW_FFT      1: an even nbin with nbin / 2 = 2^a 3^b 5^c that is
+ *                        no power of two from 64 up takes the mixed-radix row
+ *                        FFT (default; ppf_row_transform answers
+ *                        PPF_ROW_SMOOTH); 0: every such length takes the
+ *                        direct sums and the fit's data pass the DFT on the
+ *                        matrix cores, as every other non-power-of-two length
+ *                        does.  Powers of two from 64 up are bitwise the same
+ *                        under either value.                                */
 #define PPF_OPT_SCAT_GRAPH 0
 #define PPF_OPT_SCAT_SPLIT 1
 #define PPF_OPT_SCAT_TAIL 2
@@ -192,7 +205,8 @@ int ppf_set_pipeline(ppf_ctx* ctx, int32_t pieces);
 #define PPF_OPT_GUESS_WAVE 4
 #define PPF_OPT_HBM_TABLES 5
 #define PPF_OPT_POST_WAVE 6
-#define PPF_NUM_OPTS 7
+#define PPF_OPT_ROW_FFT 7
+#define PPF_NUM_OPTS 8
 int ppf_set_option(ppf_ctx* ctx, int32_t option, int32_t value);
 int ppf_get_option(const ppf_ctx* ctx, int32_t option, int32_t* value);
 /* Upper bound on workspace bytes the context may hold (default 32 GiB). */
@@ -275,6 +289,24 @@ int ppf_phase_profile(ppf_ctx* ctx, int32_t enable, uint64_t* out);
 #define PPF_SPEC_STORE 1
 #define PPF_SPEC_USE 2
 int32_t ppf_spec_nhp(int32_t nbin);
+
+/* Which row transform the entry points launch for nbin under ctx's options
+ * (ctx NULL: the default options); no device needed.  *kind:
+ *   PPF_ROW_POW2    a power of two from 64 up: the LDS and register FFTs;
+ *   PPF_ROW_SMOOTH  an even nbin with nbin / 2 = 2^a 3^b 5^c (96, 100, 768,
+ *                   1000, 1536, 2000, 3000, 6144, 8000, ...; 16 and 32 too):
+ *                   the mixed-radix LDS FFT, O(nbin log nbin) per row, in the
+ *                   row entry points and the fit's data pass
+ *                   (PPF_OPT_ROW_FFT 0: PPF_ROW_DIRECT instead);
+ *   PPF_ROW_DIRECT  every other length (odd, or a prime factor above 5 in
+ *                   nbin / 2, such as 8190): direct sums, O(nbin^2) per row.
+ * The wavelet, noise-fit-grid, Gaussian and narrowband-tau kernels use their
+ * direct sums for PPF_ROW_SMOOTH lengths as for PPF_ROW_DIRECT ones.
+ * Returns PPF_ERR_UNSUPPORTED outside [16, 8192].                           */
+#define PPF_ROW_POW2 0
+#define PPF_ROW_SMOOTH 1
+#define PPF_ROW_DIRECT 2
+int ppf_row_transform(const ppf_ctx* ctx, int32_t nbin, int32_t* kind);
 
 typedef struct {
   int32_t nsub, nchan, nbin, nmodel;

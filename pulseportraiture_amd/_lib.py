@@ -35,7 +35,8 @@ GAUSS_STATUS = {1: "converged: ftol", 2: "converged: xtol", 3: "converged: ftol 
                 -2: "non-finite residual"}
 # ppf_set_option ids (include/ppfit.h)
 OPTIONS = {"scat_graph": 0, "scat_split": 1, "scat_tail": 2, "fuse_moments": 3, "guess_wave": 4,
-           "hbm_tables": 5, "post_wave": 6}
+           "hbm_tables": 5, "post_wave": 6, "row_fft": 7}
+ROW_TRANSFORMS = ("pow2", "smooth", "direct")  # PPF_ROW_*
 PPF_PHASE_N = 32
 
 _dp = ctypes.c_void_p  # device pointers travel as plain addresses
@@ -107,6 +108,8 @@ EXPORTS = {
     "ppf_rotate_fscrunch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_spec_nhp": ([ctypes.c_int32], ctypes.c_int32),
+    "ppf_row_transform": ([ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)],
+                          ctypes.c_int),
     "ppf_irfft_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp],
                        ctypes.c_int),
     "ppf_noise_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp],

@@ -30,7 +30,8 @@ DEPS = ["ppfit_lib.hip", "ppfit_spectra.hip", "ppfit_fit.hip", "ppfit_taylor.hip
         "ppfit_gauss.hip", "ppfit_gbank.hip", "ppfit_swt.hip", "ppfit_nbscat.hip",
         "ppfit_capi.hip", "ppfit_capi_fit.hip", "ppfit_capi_rows.hip", "ppfit_capi_pca.hip",
         "ppfit_capi_swt.hip", "ppfit_capi_gauss.hip", "ppfit_host.hpp", "ppfit_wsplan.hpp",
-        "ppfit_kernels.hpp", "ppfit_device.hpp", "ppfit_rowfft.hpp", "ppfit_vthread.hpp"]
+        "ppfit_kernels.hpp", "ppfit_device.hpp", "ppfit_rowfft.hpp", "ppfit_smoothfft.hpp",
+        "ppfit_vthread.hpp"]
 OUT = os.path.join(HERE, "libppfit.so")
 FITS_OUT = os.path.join(HERE, "libppfits.so")
 TIM_OUT = os.path.join(HERE, "libpptim.so")

@@ -96,8 +96,9 @@ struct FitLaunch {
 // The stages of a fit over n subints on st, each under its kernel id's event
 // bracket.  Both schedules of ppf_fit_portrait_batch are made of these.
 
-// The data pass.  Generic length: every row's rfft on the matrix cores into
-// the X rows, then the per-subint pass (ppfit_generic.hip) (data-spectrum
+// The data pass.  Generic length: every row's rfft -- the mixed-radix FFT
+// where the length has one, else the DFT on the matrix cores -- into the X
+// rows, then the per-subint pass (ppfit_generic.hip) (data-spectrum
 // cache: the spectra into the cache's rows under STORE; under USE they are
 // there already).
 int stage_data(ppf_ctx* ctx, hipStream_t st, int n, const SpecArgs& sa, const FitLaunch& L) {
@@ -108,13 +109,17 @@ int stage_data(ppf_ctx* ctx, hipStream_t st, int n, const SpecArgs& sa, const Fi
       const double* rows = sa.data + (size_t)sa.sub0 * sa.nchan * nbin;
       const dim3 g((nrows + kGenRows - 1) / kGenRows, (NH + 255) / 256);
       double2* dst = sa.D ? sa.D : sa.X;
-      if (sa.spec_mode != PPF_SPEC_USE) {
-        if (nbin <= kGenLdsTw)
-          hipLaunchKernelGGL(k_dft_rows_mfma<true>, g, dim3(kBlock), dft_mfma_lds(nbin, true), st,
-                             rows, dst, nrows, nbin, sa.NHP, sa.tw);
-        else
-          hipLaunchKernelGGL(k_dft_rows_mfma<false>, g, dim3(kBlock), dft_mfma_lds(nbin, false),
-                             st, rows, dst, nrows, nbin, sa.NHP, sa.tw);
+      if (sa.spec_mode == PPF_SPEC_USE) {
+        // the spectra are in the cache
+      } else if (L.logN == kLogNSmooth) {
+        SMOOTH_SWITCH(nbin, hipLaunchKernelGGL(k_data_fft_rows<Row>, dim3(nrows), dim3(kBlock),
+                                               lds(kLdsRow), st, rows, dst, sa.NHP, sa.tw, row));
+      } else if (nbin <= kGenLdsTw) {
+        hipLaunchKernelGGL(k_dft_rows_mfma<true>, g, dim3(kBlock), dft_mfma_lds(nbin, true), st,
+                           rows, dst, nrows, nbin, sa.NHP, sa.tw);
+      } else {
+        hipLaunchKernelGGL(k_dft_rows_mfma<false>, g, dim3(kBlock), dft_mfma_lds(nbin, false),
+                           st, rows, dst, nrows, nbin, sa.NHP, sa.tw);
       }
       hipLaunchKernelGGL(k_data_post_gen, dim3(n), dim3(kBlock), 0, st, sa, nbin);
     }

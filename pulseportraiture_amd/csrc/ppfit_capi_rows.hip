@@ -531,6 +531,15 @@ int32_t ppf_spec_nhp(int32_t nbin) {
   return nharm_pad(nbin);
 }
 
+int ppf_row_transform(const ppf_ctx* ctx, int32_t nbin, int32_t* kind) {
+  if (!kind) return PPF_ERR_INVALID;
+  if (nbin < 16 || nbin > 8192) return PPF_ERR_UNSUPPORTED;
+  static_assert(kRowPow2 == PPF_ROW_POW2 && kRowSmooth == PPF_ROW_SMOOTH &&
+                kRowDirect == PPF_ROW_DIRECT, "ppfit.h names row_kind's values");
+  *kind = row_kind(nbin, ctx ? ctx->opt[PPF_OPT_ROW_FFT] != 0 : true);
+  return PPF_OK;
+}
+
 int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan, int32_t nbin,
                                const double* spec, const double* phase, const double* weight,
                                double* accum) {

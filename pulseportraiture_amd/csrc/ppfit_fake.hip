@@ -207,5 +207,7 @@ PPF_INST_FAKE(10)
 PPF_INST_FAKE(11)
 PPF_INST_FAKE(12)
 template __global__ void k_fake<RowAny, false>(FakeArgs, const double2*, RowAny);
+template __global__ void k_fake<RowSmooth<1024>, false>(FakeArgs, const double2*, RowSmooth<1024>);
+template __global__ void k_fake<RowSmooth<4096>, false>(FakeArgs, const double2*, RowSmooth<4096>);
 
 }  // namespace ppf

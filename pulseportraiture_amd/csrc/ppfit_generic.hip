@@ -10,7 +10,9 @@
 // O(nbin log nbin).  What has no power-of-two twin is here: the fit's data
 // pass forms all bins D_k = sum_m x_m e^{-2 pi i m k / nbin} of a chunk as a
 // GEMM on the fp64 matrix cores against the twiddle table (k_dft_rows_mfma),
-// and k_data_post_gen turns them into the fit's inputs.
+// and k_data_post_gen turns them into the fit's inputs.  An even nbin with
+// nbin / 2 = 2^a 3^b 5^c has a mixed-radix FFT (RowSmooth): there
+// k_data_fft_rows takes the GEMM's place, into the same rows.
 #include "ppfit_kernels.hpp"
 
 namespace ppf {
@@ -149,8 +151,26 @@ __global__ __launch_bounds__(kBlock) void k_dft_rows_mfma(const double* __restri
     }
 }
 
+// The same spectra for a length with a mixed-radix FFT (RowSmooth): one
+// workgroup per row, bins k < nbin/2 + 1 into row r of D (stride NHP).
+template <class Row>
+__global__ __launch_bounds__(kBlock) void k_data_fft_rows(const double* __restrict__ rows,
+                                                          double2* __restrict__ D, int NHP,
+                                                          const double2* __restrict__ tw, Row row) {
+  __shared__ typename Row::template Lds<kLdsRow> sm;
+  typename Row::Dev t(row, sm, tw);
+  const size_t r = blockIdx.x;
+  const int NH = t.nh();
+  t.load(rows + r * t.nbin());
+  for (int k = threadIdx.x; k < NH; k += kBlock) D[r * NHP + k] = t.bin(k);
+}
+#define PPF_INST_DATA_FFT(R) \
+  template __global__ void k_data_fft_rows<R>(const double*, double2*, int, const double2*, R);
+PPF_INST_DATA_FFT(RowSmooth<1024>)
+PPF_INST_DATA_FFT(RowSmooth<4096>)
+
 // The data pass's per-subint part (k_data_xspec's outputs for any nbin) from
-// the spectra k_dft_rows_mfma left in the X rows -- or, with the data-spectrum
+// the spectra k_dft_rows_mfma or k_data_fft_rows left in the X rows -- or, with the data-spectrum
 // cache (a.D), in the cache's rows: sig, dsum, the guess average R (each R_k
 // summed by one thread in channel order) and X = D conj(M) (0 at k = 0 and
 // past nbin/2), in place or into X.  As k_data_xspec: under PPF_SPEC_STORE /

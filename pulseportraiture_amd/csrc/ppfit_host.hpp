@@ -73,7 +73,7 @@ struct ppf_ctx {
   double* trace = nullptr;  // solver trace buffer (ppf_set_trace), device
   int trace_cap = 0;
   // launch-schedule options (ppf_set_option; include/ppfit.h)
-  int opt[PPF_NUM_OPTS] = {1, 1, 512, 1, 1, 0, 1};
+  int opt[PPF_NUM_OPTS] = {1, 1, 512, 1, 1, 0, 1, 1};
   double ktime[PPF_NUM_KERNELS] = {0};
   int64_t klaunch[PPF_NUM_KERNELS] = {0};
   // ppf_pca_gram_portraits under timing: mean pass, Gram tiles, slab sum, Jacobi, emit
@@ -107,13 +107,22 @@ int ilog2_exact(int v) {
 }
 
 // Any nbin in [16, 8192]: *logN = log2(nbin / 2) selects the FFT kernels of
-// a power of two from 64 up (RowPow2<logN>), -1 the direct sums (RowAny) for
-// every other length.
+// a power of two from 64 up (RowPow2<logN>); every other length gets a
+// negative value that names its row transform -- kLogNSmooth the mixed-radix
+// FFT (RowSmooth), kLogNDirect the direct sums (RowAny) -- by the one
+// predicate row_kind (ppfit_smoothfft.hpp) under the context's option
+// row_fft (no context: the default).  Only ROW_SWITCH and the fit's data pass
+// tell the two apart; to every other site logN < 0 means "not a power of
+// two", whichever it is.
+constexpr int kLogNDirect = -1, kLogNSmooth = -2;
 int check_nbin_any(ppf_ctx* ctx, int nbin, int* logN) {
   if (nbin < 16 || nbin > 8192)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin=%d: outside [16, 8192]", nbin);
-  const int l = ilog2_exact(nbin);
-  *logN = l < 6 ? -1 : l - 1;
+  switch (row_kind(nbin, ctx ? ctx->opt[PPF_OPT_ROW_FFT] != 0 : true)) {
+    case kRowPow2: *logN = ilog2_exact(nbin) - 1; break;
+    case kRowSmooth: *logN = kLogNSmooth; break;
+    default: *logN = kLogNDirect; break;
+  }
   return PPF_OK;
 }
 
@@ -282,18 +291,32 @@ int row_device(ppf_ctx* ctx, int nbin, RowPlan* rp) {
 
 // The row kernels (ppfit_rowfft.hpp): the body sees the policy as Row, the
 // kernel's last argument `row`, and lds(U), the dynamic LDS of a kernel that
-// declares Row::Lds<U>.
+// declares Row::Lds<U>.  L is check_nbin_any's logN.
+#define ROW_ARM(ROW, INIT, NBIN, ...)                                        \
+  {                                                                          \
+    using Row = ROW;                                                         \
+    const Row row INIT;                                                      \
+    auto lds = [&](RowLds u) { return Row::lds(NBIN, u); };                  \
+    __VA_ARGS__;                                                             \
+  }
+// the RowSmooth size class of NBIN
+#define SMOOTH_SWITCH(NBIN, ...)                                             \
+  do {                                                                       \
+    SmoothPlan plan_;                                                        \
+    smooth_plan(NBIN, &plan_);                                               \
+    if (smooth_class(plan_.n) == 1024)                                       \
+      ROW_ARM(RowSmooth<1024>, {plan_}, NBIN, __VA_ARGS__)                   \
+    else                                                                     \
+      ROW_ARM(RowSmooth<4096>, {plan_}, NBIN, __VA_ARGS__)                   \
+  } while (0)
 #define ROW_SWITCH(L, NBIN, ...)                                             \
   do {                                                                       \
-    if ((L) < 0) {                                                           \
-      using Row = RowAny;                                                    \
-      const Row row{NBIN};                                                   \
-      auto lds = [&](RowLds u) { return Row::lds(NBIN, u); };                \
-      __VA_ARGS__;                                                           \
+    if ((L) == kLogNSmooth) {                                                \
+      SMOOTH_SWITCH(NBIN, __VA_ARGS__);                                      \
+    } else if ((L) < 0) {                                                    \
+      ROW_ARM(RowAny, {NBIN}, NBIN, __VA_ARGS__)                             \
     } else {                                                                 \
-      LOGN_SWITCH(L, using Row = RowPow2<LG>; const Row row{};               \
-                  auto lds = [&](RowLds u) { return Row::lds(NBIN, u); };    \
-                  __VA_ARGS__)                                               \
+      LOGN_SWITCH(L, ROW_ARM(RowPow2<LG>, {}, NBIN, __VA_ARGS__))            \
     }                                                                        \
   } while (0)
 

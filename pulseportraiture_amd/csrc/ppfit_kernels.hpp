@@ -849,7 +849,7 @@ struct ResidArgs {
 // kernel declarations
 // ---------------------------------------------------------------------------
 __global__ void k_twiddles(double2* tw, int nbin);
-// row kernels: Row = RowPow2<LOGN> or RowAny (ppfit_rowfft.hpp)
+// row kernels: Row = RowPow2<LOGN>, RowSmooth<MAXN> or RowAny (ppfit_rowfft.hpp)
 template <class Row>
 __global__ void k_model_spec(const double* model, double2* M, double* pn, int NHP, int zero_dc,
                              const double2* tw, double* M2, Row row);
@@ -894,6 +894,10 @@ __global__ void k_find_kc_rows(const double* pows, const double* errs, int n, in
 template <bool LTW>
 __global__ void k_dft_rows_mfma(const double* rows, double2* D, int nrows, int nbin, int NHP,
                                 const double2* tw);
+// Row = RowSmooth<MAXN> only
+template <class Row>
+__global__ void k_data_fft_rows(const double* rows, double2* D, int NHP, const double2* tw,
+                                Row row);
 __global__ void k_data_post_gen(SpecArgs a, int nbin);
 // ppf_rotate_fscrunch (ppfit_fscrunch.hip): channels per workgroup, a
 // constant of the build (the order of summation may not depend on the call)

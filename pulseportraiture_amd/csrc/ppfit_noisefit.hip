@@ -297,6 +297,8 @@ PPF_INST_NF(RowPow2<10>)
 PPF_INST_NF(RowPow2<11>)
 PPF_INST_NF(RowPow2<12>)
 PPF_INST_NF(RowAny)
+PPF_INST_NF(RowSmooth<1024>)
+PPF_INST_NF(RowSmooth<4096>)
 template __global__ void k_find_kc_rows<0>(const double*, const double*, int, int*, int*);
 template __global__ void k_find_kc_rows<1>(const double*, const double*, int, int*, int*);
 

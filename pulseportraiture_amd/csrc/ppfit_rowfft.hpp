@@ -1,9 +1,11 @@
 // ppfit_rowfft.hpp -- the row transform of the rfft-based row kernels as a
 // policy: RowPow2<LOGN> (nbin = 2^(LOGN + 1) from 64 up: the LDS FFT of
-// ppfit_device.hpp) and RowAny (every other nbin in [16, 8192]: direct sums,
-// O(nbin^2) per row).  A row kernel is one `template <class Row>` body; what
-// differs between the two -- how a bin is obtained, how a spectrum goes back
-// to samples, where a thread keeps the bins it owns, the LDS -- is here.
+// ppfit_device.hpp), RowSmooth<MAXN> (even nbin with nbin / 2 = 2^a 3^b 5^c <=
+// MAXN: the mixed-radix LDS FFT of ppfit_smoothfft.hpp) and RowAny (every
+// other nbin in [16, 8192]: direct sums, O(nbin^2) per row).  A row kernel is
+// one `template <class Row>` body; what differs between them -- how a bin is
+// obtained, how a spectrum goes back to samples, where a thread keeps the
+// bins it owns, the LDS -- is here.
 //
 // Bin k of a real row: D_k = sum_m x_m e^{-2 pi i m k / nbin}.  The direct
 // sums take one bin per thread, the phasor advancing by one complex product
@@ -13,6 +15,7 @@
 // the fitted parameters).
 #pragma once
 #include "ppfit_device.hpp"
+#include "ppfit_smoothfft.hpp"
 
 namespace ppf {
 
@@ -184,7 +187,8 @@ __device__ __forceinline__ double2 scat_div(double2 v, double w) {
 //   t.release()      every thread has taken its bins: load() may follow
 //   t.for_bins(f)    f(i, k) for the bins the thread owns, k = tid + i kBlock
 //   Row::Own         the thread's owned bins between two passes: registers
-//                    (RowPow2) or the cells of a spectrum in memory (RowAny)
+//                    (RowPow2, RowSmooth) or the cells of a spectrum in memory
+//                    (RowAny)
 //   t.inverse(own, out, epi)   out = epi(irfft of the owned bins)
 // The launch passes Row::lds(nbin, U) bytes of dynamic LDS.
 // ---------------------------------------------------------------------------
@@ -313,6 +317,140 @@ struct RowAny {
         out[2 * j] = v.x;
         if (two) out[2 * j + 1] = v.y;
       }
+    }
+  };
+};
+
+// ---------------------------------------------------------------------------
+// nbin / 2 = 2^a 3^b 5^c: the mixed-radix LDS FFT
+// ---------------------------------------------------------------------------
+// One pass of the Stockham FFT of N points in buf, all kBlock threads: every
+// butterfly's inputs to registers, a barrier, the outputs to their places, a
+// barrier (lds_fft's passes, the radix and N known at run time; MAXN bounds
+// the register arrays).
+template <int R, int MAXN, bool INV>
+__device__ __forceinline__ void smooth_pass(double2* buf, const double2* __restrict__ tw, int N,
+                                            int Ns) {
+  constexpr int B = smooth_chunks(MAXN, R);
+  const SmoothPass ps(N, R, Ns);
+  double2 v[B][R];
+#pragma unroll
+  for (int c = 0; c < B; ++c) {
+    const int j = threadIdx.x + c * kBlock;
+    if (j < ps.Q) smooth_gather<R, INV>(buf, tw, ps, j, v[c]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < B; ++c) {
+    const int j = threadIdx.x + c * kBlock;
+    if (j < ps.Q) smooth_scatter<R, INV>(buf, ps, j, v[c]);
+  }
+  __syncthreads();
+}
+
+// The transform of plan p in buf (unnormalised both ways, as lds_fft).
+template <int MAXN, bool INV>
+__device__ void smooth_fft(double2* buf, const double2* __restrict__ tw, const SmoothPlan& p) {
+  int Ns = 1;
+  for (int s = 0; s < p.npass; ++s) {
+    const int r = p.radix(s);  // uniform
+    if (r == 4) smooth_pass<4, MAXN, INV>(buf, tw, p.n, Ns);
+    else if (r == 2) smooth_pass<2, MAXN, INV>(buf, tw, p.n, Ns);
+    else if (r == 3) smooth_pass<3, MAXN, INV>(buf, tw, p.n, Ns);
+    else smooth_pass<5, MAXN, INV>(buf, tw, p.n, Ns);
+    Ns *= r;
+  }
+}
+
+// MAXN: the size class (smooth_class), N = nbin / 2 <= MAXN.  The owned bins
+// are registers and the inverse runs in the row's own buffer with the
+// epilogue per complex sample pair, as RowPow2's.  Dynamic LDS: N + 1 cells
+// (N for a row that is only transformed), twice that with a spectrum beside.
+template <int MAXN>
+struct RowSmooth {
+  SmoothPlan plan;
+  static constexpr int KI = (MAXN + 1 + kBlock - 1) / kBlock;  // bins per thread
+  static constexpr int kMaxKI = KI;
+  static constexpr bool kFft = true;
+  template <RowLds U>
+  struct Lds {};  // dynamic
+  static size_t lds(int nbin, RowLds u) {
+    const size_t N = (size_t)nbin / 2;
+    if (u == kLdsRow) return N * sizeof(double2);
+    return (u == kLdsRowSpec ? 2 : 1) * (N + 1) * sizeof(double2);
+  }
+
+  struct Own {
+    double2 v[KI];
+    __device__ __forceinline__ Own(double2*) {}
+    __device__ __forceinline__ double2& at(int i, int) { return v[i]; }
+  };
+
+  struct Dev {
+    double2 *buf, *spec;
+    const double2* tw;
+    SmoothPlan plan;
+    template <RowLds U>
+    __device__ __forceinline__ Dev(RowSmooth row, Lds<U>&, const double2* tw_)
+        : tw(tw_), plan(row.plan) {
+      extern __shared__ __align__(16) unsigned char gsm[];
+      buf = reinterpret_cast<double2*>(gsm);
+      spec = buf + (U == kLdsRowSpec ? plan.n + 1 : 0);
+    }
+    __device__ __forceinline__ int nbin() const { return 2 * plan.n; }
+    __device__ __forceinline__ int nh() const { return plan.n + 1; }
+    __device__ __forceinline__ void load(const double* __restrict__ row) {
+      const double2* r2 = reinterpret_cast<const double2*>(row);
+      for (int j = threadIdx.x; j < plan.n; j += kBlock) buf[j] = r2[j];
+      __syncthreads();
+      smooth_fft<MAXN, false>(buf, tw, plan);
+    }
+    __device__ __forceinline__ double2 bin(int k) const {
+      return smooth_rfft_post(buf, plan.n, k, tw[k]);
+    }
+    __device__ __forceinline__ void release() { __syncthreads(); }
+    __device__ __forceinline__ double* reals() { return reinterpret_cast<double*>(buf); }
+    template <class F>
+    __device__ __forceinline__ void for_bins(F&& f) {
+      const int N = plan.n;
+#pragma unroll
+      for (int i = 0; i < KI; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k <= N) f(i, k);
+      }
+    }
+    // c2r_from_spectrum at a run-time N: X_k staged in buf[0 .. N], Z_k formed
+    // in registers, the inverse passes, then epi per sample pair
+    template <class Epi = C2rPlain>
+    __device__ __forceinline__ void inverse(Own& own, double* __restrict__ out, Epi epi = Epi()) {
+      const int N = plan.n, tid = threadIdx.x;
+#pragma unroll
+      for (int i = 0; i < KI; ++i) {
+        const int k = tid + i * kBlock;
+        if (k <= N) {
+          double2 x = own.v[i];
+          if (k == 0 || k == N) x.y = 0.0;
+          buf[k] = x;
+        }
+      }
+      __syncthreads();
+      double2 z[KI];
+#pragma unroll
+      for (int i = 0; i < KI; ++i) {
+        const int k = tid + i * kBlock;
+        if (k < N) z[i] = smooth_irfft_pre(buf[k], buf[N - k], tw[k]);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < KI; ++i) {
+        const int k = tid + i * kBlock;
+        if (k < N) buf[k] = z[i];
+      }
+      __syncthreads();
+      smooth_fft<MAXN, true>(buf, tw, plan);
+      const double inv = 1.0 / (double)N;
+      double2* o2 = reinterpret_cast<double2*>(out);
+      for (int j = tid; j < N; j += kBlock) o2[j] = epi(j, cscale(buf[j], inv));
     }
   };
 };

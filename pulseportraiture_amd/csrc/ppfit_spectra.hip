@@ -849,5 +849,7 @@ PPF_INST(10)
 PPF_INST(11)
 PPF_INST(12)
 PPF_INST_ROW(RowAny)
+PPF_INST_ROW(RowSmooth<1024>)
+PPF_INST_ROW(RowSmooth<4096>)
 
 }  // namespace ppf

@@ -273,13 +273,23 @@ class Engine:
 
     def set_option(self, name, value):
         """Launch-schedule option of this context (ppf_set_option; names in
-        _lib.OPTIONS).  No setting changes a result."""
+        _lib.OPTIONS).  No setting changes a result; "row_fft" chooses
+        between two implementations of the row transform that agree to
+        rounding (row_transform)."""
         self._chk(self.lib.ppf_set_option(self.ctx, _lib.OPTIONS[name], int(value)))
 
     def get_option(self, name):
         v = ctypes.c_int32()
         self._chk(self.lib.ppf_get_option(self.ctx, _lib.OPTIONS[name], ctypes.byref(v)))
         return v.value
+
+    def row_transform(self, nbin):
+        """Which row transform this context launches for nbin: "pow2",
+        "smooth" (the mixed-radix FFT) or "direct" (ppf_row_transform)."""
+        kind = ctypes.c_int32()
+        if self.lib.ppf_row_transform(self.ctx, int(nbin), ctypes.byref(kind)):
+            raise PPFitError("nbin=%d: outside [16, 8192]" % nbin)
+        return _lib.ROW_TRANSFORMS[kind.value]
 
     def set_timing(self, on=True):
         self._chk(self.lib.ppf_set_timing(self.ctx, int(bool(on))))
