@@ -730,7 +730,9 @@ int ppf_unpack_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, 
  *   t[j] = sum_{n: w[s][n] != 0} w[s][n] sum_{p < ntot} data[s][p][n][j]
  * gives the off-pulse window [j0, j0 + width) (circular) of smallest sum,
  * first on ties; every profile data[s][p][n] then has its mean over that
- * window subtracted.  data [nsub][npol][nchan][nbin] (nbin <= 8192),
+ * window subtracted.  A window whose sum is NaN never wins; if no window
+ * has an ordered sum (every sum NaN), the window starts at 0.
+ * data [nsub][npol][nchan][nbin] (nbin <= 8192),
  * weights [nsub][nchan]; window [nsub] receives j0 (NULL: not written).
  * Callers pass width = floor(0.15 nbin), PSRCHIVE's default duty cycle.   */
 int ppf_remove_baseline(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
@@ -742,7 +744,10 @@ int ppf_remove_baseline(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan,
  * them, pptoas.py:401).  Restated from PSRCHIVE's default "phase" S/N
  * estimator (PSRCHIVE is not in this image: PARITY UNPINNED):
  *   off-pulse window: the circular run of `width` bins with the smallest
- *     sum (first on ties; windows summed bin by bin from their start);
+ *     sum (first on ties; windows summed bin by bin from their start); a
+ *     window whose sum is NaN never wins, and if no window has an ordered
+ *     sum the window starts at 0 (a row with a NaN bin then has C = NaN
+ *     and snr 0);
  *   m, v: mean and sample variance (n - 1) over that window;
  *   edges (cumulative-power peak): with y the profile minus m read
  *     circularly from the bin after the window, c its running sum and

@@ -110,25 +110,35 @@ def rotate_data(data, phase=0.0, DM=0.0, Ps=None, freqs=None, nu_ref=np.inf):
     return out.reshape(data.shape) if ndim in (1, 2) else out
 
 
-def remove_baseline(subints, weights, ntot=1, duty=0.15):
+def _first_min(box):
+    """Index of the smallest ordered value, first on ties.  A NaN never wins;
+    with no ordered value at all the index is 0 (include/ppfit.h)."""
+    ok = np.flatnonzero(~np.isnan(box))
+    return int(ok[np.argmin(box[ok])]) if len(ok) else 0
+
+
+def remove_baseline(subints, weights, ntot=1, duty=0.15, width=None):
     """arch.remove_baseline() as load_data calls it (pplib.py:2691), restated
     from PSRCHIVE's documented default (Integration::remove_baseline with the
     BaselineWindow estimator, duty cycle 0.15): per subint, the off-pulse
     window is the circular run of floor(duty * nbin) bins with the smallest
     sum of the total-intensity profile (weighted frequency sum of the first
     ntot polarisations; first window on ties), and every profile has its mean
-    over that window subtracted.  PARITY UNPINNED: PSRCHIVE is not in this
-    image and the reference ships no archives.  Returns (out, window starts)."""
+    over that window subtracted.  width, when given, is the window's length in
+    bins as the ABI takes it (duty is then unused).  A window whose sum is NaN
+    never wins; with every sum NaN the window starts at 0.  PARITY UNPINNED:
+    PSRCHIVE is not in this image and the reference ships no archives.
+    Returns (out, window starts)."""
     d = np.array(subints, dtype=float)
     nsub, npol, nchan, nbin = d.shape
-    width = max(1, int(duty * nbin))
+    width = max(1, int(duty * nbin)) if width is None else int(width)
     w = np.asarray(weights, dtype=float)
     starts = np.zeros(nsub, dtype=int)
     for s in range(nsub):
         on = w[s] != 0.0
         t = np.einsum("n,nj->j", w[s][on], d[s, :ntot][:, on].sum(axis=0))
         box = np.array([t[(j + np.arange(width)) % nbin].sum() for j in range(nbin)])
-        j0 = int(np.argmin(box))
+        j0 = _first_min(box)
         idx = (j0 + np.arange(width)) % nbin
         d[s] -= d[s][..., idx].mean(axis=-1)[..., None]
         starts[s] = j0
@@ -159,7 +169,7 @@ def profile_snr(rows, duty=0.15, threshold=0.1):
         box = np.zeros(nbin)
         for i in range(width):  # sequential per window start, as the device
             box = box + row[(np.arange(nbin) + i) % nbin]
-        j0 = int(np.argmin(box))
+        j0 = _first_min(box)  # NaN sums never win; all NaN: start 0
         win = row[(j0 + np.arange(width)) % nbin]
         m = 0.0
         for v_ in win:

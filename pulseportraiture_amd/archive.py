@@ -453,7 +453,10 @@ class Archive:
             ph = self.rot_sign * dedispersion_phases(r.freqs[lo:hi], r.Ps[lo:hi], r.DM, r.nu0)
             eng.rotate_rows(d, np.repeat(ph[:, None, :], npol, axis=1), inplace=True)
         if self.rm_base:
-            ntot = 2 if (npol >= 2 and str(r.get("state", "")).upper().startswith("COH")) else 1
+            # total intensity as pscrunch forms it: the state is PSRCHIVE's name
+            # (registered bunches) or the POL_TYPE a PSRFITS source reports
+            from .psrfits import total_npol
+            ntot = total_npol(npol, r.get("state", "Intensity"))
             eng.remove_baseline(d, r.weights[lo:hi], ntot=ntot, duty=DUTY_CYCLE)
         return d
 

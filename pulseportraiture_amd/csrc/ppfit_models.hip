@@ -386,6 +386,9 @@ __global__ __launch_bounds__(256) void k_remove_baseline(double* __restrict__ da
     int j0 = bi[0];
     for (int q = 1; q < 4; ++q)
       if (bv[q] < b || (bv[q] == b && bi[q] < j0)) { b = bv[q]; j0 = bi[q]; }
+    // a NaN sum never wins a comparison: with no ordered sum at all the
+    // sentinel survives, and the window starts at 0 (include/ppfit.h)
+    if (j0 == 0x7fffffff) j0 = 0;
     s_j0 = j0;
     if (win_out) win_out[s] = j0;
   }
@@ -441,7 +444,8 @@ __global__ __launch_bounds__(64) void k_profile_snr(const double* __restrict__ r
     const int oj = __shfl_xor(bj, o);
     if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
   }
-  const int j0 = bj;
+  // no window with an ordered (non-NaN) sum: the sentinel survives, start at 0
+  const int j0 = bj == 0x7fffffff ? 0 : bj;
   // window mean and sample variance (serial over the window, lane 0's order
   // is the window's own: one pass for the mean, one for the squares)
   double m = 0.0, v = 0.0;

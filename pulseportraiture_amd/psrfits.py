@@ -272,15 +272,24 @@ def polyco_period(pc, mjd):
     return 1.0 / (pc["ref_f0"][i] + df / 60.0)
 
 
+def total_npol(npol, state):
+    """How many leading polarisations sum to the total intensity: 2 (AA + BB)
+    for coherence and 2-pol data, 1 for Stokes (I) and intensity data.  state
+    is a PSRFITS POL_TYPE (AABBCRCI, AABB, IQUV, AA+BB, ...) or PSRCHIVE's
+    name of the state (Coherence, PPQQ, Stokes, Intensity).  pscrunch and
+    remove_baseline both take the total from here."""
+    st = str(state).upper()
+    if npol < 2 or st.startswith(("IQUV", "STOKE", "INTENS", "AA+BB")):
+        return 1
+    return 2
+
+
 def pscrunch_mode(npol, pol_type):
     """ppf_unpack_subints pmode of pscrunch for a PSRFITS POL_TYPE: coherence
     (AABBCRCI) and 2-pol (AABB) sum AA + BB; Stokes (IQUV) keep I."""
     if npol == 1:
         return 0
-    pt = pol_type.upper()
-    if pt.startswith("IQUV") or pt == "STOKE":
-        return 2
-    return 1
+    return 1 if total_npol(npol, pol_type) == 2 else 2
 
 
 class PSRFITSSource:
