@@ -10,6 +10,9 @@
  *   ppf_fit_portrait_batch  <- pptoaslib.fit_portrait_full   pptoaslib.py:928-1096
  *                              (+ the get_TOAs initial guess pptoas.py:420-456,
  *                               ppalign.py:180-185, batched over subints)
+ *   ppf_fit_portrait_batch_raw <- the same on 16-bit PSRFITS samples: load_data's
+ *                              scale / offset / pscrunch (pplib.py:2670-2732)
+ *                              inside the fit's data pass
  *   ppf_phase_shift_batch   <- pplib.fit_phase_shift          pplib.py:2054-2100
  *   ppf_phase_tau_batch     <- pptoaslib.fit_portrait_full on one channel with
  *                              fit_flags [1,0,0,1,0]: the fit_phase_shift_scat
@@ -376,6 +379,31 @@ typedef struct {
 int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* desc,
                            const ppf_fit_result* out);
 
+/* The same fit straight from PSRFITS samples: the data pass reads the 16-bit
+ * samples and forms value = raw * scl + offs (the polarisation sum of pmode
+ * 1 included) as it loads each row, so no fp64 copy of the data exists.
+ * Every output is bit for bit that of ppf_unpack_subints followed by
+ * ppf_fit_portrait_batch.  desc is ppf_fit_desc unchanged, with desc->data
+ * NULL (else PPF_ERR_INVALID); everything else of the call -- methods, flags,
+ * masks, the data-spectrum cache, the chunk loop -- is as there.
+ * PPF_ERR_UNSUPPORTED unless raw_type is PPFITS_RAW_I16 and nbin is a power
+ * of two in [64, 8192] (unpack and call ppf_fit_portrait_batch for those);
+ * PPF_ERR_INVALID for pmode outside 0..2, ipol >= npol, pmode 1 with npol < 2
+ * or raw not 16-byte aligned.                                              */
+typedef struct {
+  int32_t raw_type;   /* PPFITS_RAW_* of ppfits.h; PPFITS_RAW_I16 here        */
+  int32_t npol;       /* polarisations stored per subint                      */
+  int32_t pmode;      /* as ppf_unpack_subints: 0 one polarisation (ipol),
+                         1 AA + BB (p = 0 and 1), 2 the first (Stokes I)      */
+  int32_t ipol;       /* pmode 0: which polarisation is fitted                */
+  const void*   raw;  /* [nsub][npol][nchan][nbin]                            */
+  const double* scl;  /* [nsub][npol][nchan]                                  */
+  const double* offs; /* [nsub][npol][nchan]                                  */
+} ppf_raw_subints;
+
+int ppf_fit_portrait_batch_raw(ppf_ctx* ctx, const ppf_fit_desc* desc,
+                               const ppf_raw_subints* raw, const ppf_fit_result* out);
+
 /* ---------------------------------------------------------------------- */
 /* fit_phase_shift over nprof profiles (pplib.py:2054-2100).              */
 /* out[nprof][6] = phase, phase_err, scale, scale_err, snr, red_chi2       */
@@ -719,7 +747,9 @@ int ppf_tscrunch(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_
  * raw_type (ppfits.h PPFITS_RAW_*: 1 uint8, 2 int16, 3 float32), scl and
  * offs [nsub][npol][nchan] (DAT_SCL, DAT_OFFS); value = raw * scl + offs.
  * pmode 0 keeps every polarisation, 1 sums the first two (AA + BB), 2 takes
- * the first (Stokes I); out [nsub][pmode ? 1 : npol][nchan][nbin].        */
+ * the first (Stokes I); out [nsub][pmode ? 1 : npol][nchan][nbin].
+ * A fit needs no such copy of 16-bit samples: ppf_fit_portrait_batch_raw
+ * reads them in its data pass.                                            */
 int ppf_unpack_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
                        int32_t raw_type, const void* raw, const double* scl, const double* offs,
                        int32_t pmode, double* out);

@@ -69,6 +69,16 @@ class FitResult(ctypes.Structure):
                 ("grad", _dp), ("hess", _dp), ("errs_out", _dp)]
 
 
+class RawSubintsDesc(ctypes.Structure):
+    """ppf_raw_subints."""
+    _fields_ = [("raw_type", ctypes.c_int32), ("npol", ctypes.c_int32),
+                ("pmode", ctypes.c_int32), ("ipol", ctypes.c_int32),
+                ("raw", _dp), ("scl", _dp), ("offs", _dp)]
+
+
+# ppfits.h PPFITS_RAW_*
+RAW_U8, RAW_I16, RAW_F32 = 1, 2, 3
+
 EXPORTS = {
     "ppf_version": ([], ctypes.c_int),
     "ppf_ctx_create": ([ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
@@ -93,6 +103,9 @@ EXPORTS = {
                           ctypes.c_int),
     "ppf_fit_portrait_batch": ([ctypes.c_void_p, ctypes.POINTER(FitDesc),
                                 ctypes.POINTER(FitResult)], ctypes.c_int),
+    "ppf_fit_portrait_batch_raw": ([ctypes.c_void_p, ctypes.POINTER(FitDesc),
+                                    ctypes.POINTER(RawSubintsDesc),
+                                    ctypes.POINTER(FitResult)], ctypes.c_int),
     "ppf_phase_shift_batch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                _dp, _dp, _dp, _dp, ctypes.c_int32,
                                ctypes.c_double, ctypes.c_double, _dp], ctypes.c_int),

@@ -479,6 +479,21 @@ class Archive:
         sub = self._reg.base.subints
         return sub if _is_tensor(sub) else None
 
+    def read_raw(self, lo=0, hi=None):
+        """Subints lo:hi as an engine.RawSubints (a PSRFITS file's samples
+        with their scales and offsets, on the device), or None when the
+        request processes the data -- dedispersion, baseline removal,
+        tscrunch -- or the source is not a PSRFITS file: read() then."""
+        if self.tscrunch or self.rot_sign or self.rm_base or self._reg is not None:
+            return None
+        src = _source(*self._src_args)
+        try:
+            if not hasattr(src, "read_raw"):
+                return None
+            return src.read_raw(lo, self.meta.nsub if hi is None else hi)
+        finally:
+            src.close()
+
     def read(self, lo=0, hi=None):
         if self.tscrunch:  # the one averaged subint needs every raw subint
             from .engine import get_engine

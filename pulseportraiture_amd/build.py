@@ -43,7 +43,8 @@ def _lib_specs():
     """(output, compiler command without -D/-o, dependency files) per library."""
     hip = ([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + INC,
             "-I" + CSRC, os.path.join(CSRC, SOURCES[0])],
-           [os.path.join(CSRC, f) for f in DEPS] + [os.path.join(INC, "ppfit.h")])
+           [os.path.join(CSRC, f) for f in DEPS] + [os.path.join(INC, "ppfit.h"),
+                                                     os.path.join(INC, "ppfits.h")])
     fits = ([CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + INC,
              os.path.join(CSRC, "psrfits.cpp"), os.path.join(CSRC, "psrfits_write.cpp")],
             [os.path.join(CSRC, "psrfits.cpp"), os.path.join(CSRC, "psrfits_write.cpp"),

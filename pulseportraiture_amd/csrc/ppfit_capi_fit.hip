@@ -1,6 +1,7 @@
-// ppfit_capi_fit.hip -- ppf_fit_portrait_batch: workspace plan, stages,
-// argument binding and the two launch schedules.
+// ppfit_capi_fit.hip -- ppf_fit_portrait_batch and ppf_fit_portrait_batch_raw:
+// workspace plan, stages, argument binding and the two launch schedules.
 #include "ppfit_host.hpp"
+#include "ppfits.h"  // PPFITS_RAW_*
 
 namespace {
 
@@ -123,7 +124,15 @@ int stage_data(ppf_ctx* ctx, hipStream_t st, int n, const SpecArgs& sa, const Fi
       }
       hipLaunchKernelGGL(k_data_post_gen, dim3(n), dim3(kBlock), 0, st, sa, nbin);
     }
-    LOGN_SWITCH(L.logN, WIDE_SWITCH(L.wide, hipLaunchKernelGGL((k_data_xspec<LG, WD>), dim3(n),
+    const dim3 g(n);
+    if (sa.raw) {  // rows of 16-bit samples (ppf_fit_portrait_batch_raw)
+      LOGN_SWITCH(L.logN,
+                  WIDE_SWITCH(L.wide, hipLaunchKernelGGL((k_data_xspec<LG, WD, true>), g,
+                                                         dim3(XspecCfg<LG>::WPB * 64),
+                                                         L.lds_xspec, st, sa)));
+      return;
+    }
+    LOGN_SWITCH(L.logN, WIDE_SWITCH(L.wide, hipLaunchKernelGGL((k_data_xspec<LG, WD, false>), g,
                                                                dim3(XspecCfg<LG>::WPB * 64),
                                                                L.lds_xspec, st, sa)));
   });
@@ -303,8 +312,10 @@ bool fit_is_taylor(const ppf_fit_desc* d) {
 }
 
 // The descriptor and result checks of ppf_fit_portrait_batch (nsub > 0);
-// *logN as check_nbin_any gives it.
-int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o, int* logN) {
+// *logN as check_nbin_any gives it.  raw: the data are its samples, not
+// d->data.
+int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_raw_subints* raw,
+                   const ppf_fit_result* o, int* logN) {
   if (d->nchan <= 0 || d->nchan > PPF_MAX_NCHAN)
     return fail(ctx, PPF_ERR_UNSUPPORTED, "nchan=%d outside [1, %d]", d->nchan, PPF_MAX_NCHAN);
   if (d->nmodel <= 0) return fail(ctx, PPF_ERR_INVALID, "nmodel must be >= 1");
@@ -316,7 +327,12 @@ int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o,
     return fail(ctx, PPF_ERR_INVALID, "legacy TNC fits phase and DM only (fit_flags [1,1,0,0,0])");
   if (d->solver_flags & ~(PPF_SOLVE_EXACT | PPF_SOLVE_EVAL | PPF_GUESS_DIRECT))
     return fail(ctx, PPF_ERR_INVALID, "unknown solver_flags bits 0x%x", d->solver_flags);
-  if (!d->data || !d->model || !d->freqs || !d->P || !d->init || !d->nu_fit || !d->nu_out)
+  if (raw && d->data)
+    return fail(ctx, PPF_ERR_INVALID, "a raw fit takes its data from the samples: desc->data "
+                "must be NULL");
+  if (raw && (!raw->raw || !raw->scl || !raw->offs))
+    return fail(ctx, PPF_ERR_INVALID, "missing required input pointer");
+  if ((!raw && !d->data) || !d->model || !d->freqs || !d->P || !d->init || !d->nu_fit || !d->nu_out)
     return fail(ctx, PPF_ERR_INVALID, "missing required input pointer");
   if (!o->params || !o->param_errs || !o->nu_out || !o->cov || !o->scales || !o->scale_errs ||
       !o->channel_snrs || !o->chi2 || !o->red_chi2 || !o->snr || !o->nfev || !o->status)
@@ -325,6 +341,21 @@ int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o,
   // nbin not a power of two: the generic-length data pass and template
   // spectra (ppfit_generic.hip); every solver kernel takes any nbin
   if (int r = check_nbin_any(ctx, d->nbin, logN)) return r;
+  if (raw) {
+    // the raw rows exist for the power-of-two data pass and 16-bit samples
+    if (*logN < 0)
+      return fail(ctx, PPF_ERR_UNSUPPORTED, "raw samples: nbin=%d is not a power of two in "
+                  "[64, 8192] (unpack and fit the values)", d->nbin);
+    if (raw->raw_type != PPFITS_RAW_I16)
+      return fail(ctx, PPF_ERR_UNSUPPORTED, "raw samples: raw_type %d, only 16-bit samples "
+                  "(PPFITS_RAW_I16) are read in the fit", raw->raw_type);
+    if (raw->npol < 1 || raw->pmode < 0 || raw->pmode > 2 || raw->ipol < 0 ||
+        raw->ipol >= raw->npol || (raw->pmode == 1 && raw->npol < 2))
+      return fail(ctx, PPF_ERR_INVALID, "raw samples: pmode %d, ipol %d with npol %d",
+                  raw->pmode, raw->ipol, raw->npol);
+    if (reinterpret_cast<uintptr_t>(raw->raw) % 16)
+      return fail(ctx, PPF_ERR_INVALID, "raw samples must be 16-byte aligned");
+  }
   // data-spectrum cache: sig, dsum and R live in the caller's arrays, and
   // Taylor-path subints keep D instead of X (ppfit.h, PPF_SPEC_*)
   const int smode = d->spec_mode;
@@ -344,14 +375,23 @@ int check_fit_desc(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o,
 // Everything of the two argument structs that comes from the descriptor, the
 // result struct and the context's settings (templates and tables:
 // fit_tables; workspace pointers: FitWorkspace::slice).
-void bind_fit_args(const ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o,
-                   SpecArgs& sa, FitArgs& fa) {
+void bind_fit_args(const ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_raw_subints* raw,
+                   const ppf_fit_result* o, SpecArgs& sa, FitArgs& fa) {
   const int nbin = d->nbin;
   sa.nchan = fa.nchan = d->nchan;
   sa.NHP = fa.NHP = nharm_pad(nbin);
   sa.kc = fa.kc = noise_kc(nbin);
   sa.guess = fa.guess = d->guess;
   sa.data = d->data;
+  if (raw) {
+    sa.raw = static_cast<const uint32_t*>(raw->raw);
+    sa.scl = raw->scl;
+    sa.offs = raw->offs;
+    sa.rnpol = raw->npol;
+    sa.rp0 = raw->pmode == 0 ? raw->ipol : 0;
+    sa.rsum = raw->pmode == 1 ? 1 : 0;
+    sa.rp1 = sa.rsum ? 1 : sa.rp0;
+  }
   sa.model_idx = fa.model_idx = d->model_idx;
   sa.freqs = fa.freqs = d->freqs;
   sa.errs = d->errs;
@@ -433,23 +473,19 @@ int fit_tables(ppf_ctx* ctx, const ppf_fit_desc* d, SpecArgs& sa, FitArgs& fa) {
   return PPF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-// ---------------------------------------------------------------------------
-int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o) {
-  if (!ctx || !d || !o) return fail(ctx, PPF_ERR_INVALID, "null argument");
+// The fit call of both entry points; raw NULL: the data are d->data.
+int fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_raw_subints* raw,
+                       const ppf_fit_result* o) {
   if (d->nsub <= 0) return PPF_OK;
   FitLaunch L;
-  if (int r = check_fit_desc(ctx, d, o, &L.logN)) return r;
+  if (int r = check_fit_desc(ctx, d, raw, o, &L.logN)) return r;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int nchan = d->nchan, nbin = d->nbin, NH = nbin / 2 + 1;
   const bool tnc = fit_is_tnc(d), ncg = d->method == PPF_METHOD_NEWTON_CG;
   const bool exact = fit_is_exact(d), taylor = fit_is_taylor(d);
   SpecArgs sa{};
   FitArgs fa{};
-  bind_fit_args(ctx, d, o, sa, fa);
+  bind_fit_args(ctx, d, raw, o, sa, fa);
   if (int r = fit_tables(ctx, d, sa, fa)) return r;
 
   // per-channel tables in HBM (the WIDE kernels, ppfit_kernels.hpp chan_tables)
@@ -592,6 +628,22 @@ int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_re
     if (int r = stage_errs(ctx, st, nc, sa, o->errs_out)) return r;
   }
   return PPF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+int ppf_fit_portrait_batch(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_fit_result* o) {
+  if (!ctx || !d || !o) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  return fit_portrait_batch(ctx, d, nullptr, o);
+}
+
+int ppf_fit_portrait_batch_raw(ppf_ctx* ctx, const ppf_fit_desc* d, const ppf_raw_subints* raw,
+                               const ppf_fit_result* o) {
+  if (!ctx || !d || !raw || !o) return fail(ctx, PPF_ERR_INVALID, "null argument");
+  return fit_portrait_batch(ctx, d, raw, o);
 }
 
 }  // extern "C"

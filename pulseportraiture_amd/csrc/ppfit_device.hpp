@@ -530,6 +530,13 @@ __device__ __forceinline__ double2 ld_stream(const double2* p) {
   return *p;
 #endif
 }
+__device__ __forceinline__ uint32_t ld_stream(const uint32_t* p) {
+#if PPF_NT
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
 #ifndef PPF_NT_ST
 // ... but the write-once X stores go through the caches: with the hint they
 // measured 4.675 ms for the data pass, without it 4.556 ms (r04, same box;
@@ -588,6 +595,102 @@ struct WaveRow {
       const double2* r2 = reinterpret_cast<const double2*>(src);
 #pragma unroll 4
       for (int i = 0; i < LI; ++i) buf[lane + 64 * i] = r2[lane + 64 * i];
+    }
+  }
+};
+
+// The same walk over rows of 16-bit samples (PSRFITS DATA with DAT_SCL and
+// DAT_OFFS per row): a row is N words of two samples each, so the word at
+// index j is packed sample j and WaveRow's lane mapping carries over, one
+// word per lane where WaveRow has one double2.  The prefetched row stays
+// packed (N / 64 registers per polarisation, a quarter of the fp64 row's) and
+// becomes doubles only when the FFT takes it: fma((double)raw, scl, offs),
+// plus the second polarisation's when two are summed -- k_unpack's values
+// (ppfit_models.hip) bit for bit.  scl and offs of the row's polarisation(s)
+// travel with the row as one vector load: lane l holds entry l & 3 of (scl0,
+// offs0, scl1, offs1), read back with lane_of, so no scalar load shares the
+// FFT's LDS wait counter.
+struct RawRowSrc {
+  const uint32_t* w0;  // polarisation rp0's row
+  const uint32_t* w1;  // polarisation rp1's row (w0 again unless two are summed)
+  const double* so;    // this lane's entry of (scl0, offs0, scl1, offs1)
+};
+__device__ __forceinline__ double raw_lo(uint32_t w) { return (double)(int16_t)(w & 0xffffu); }
+__device__ __forceinline__ double raw_hi(uint32_t w) { return (double)((int32_t)w >> 16); }
+
+template <int LOGN>
+struct RawWaveRow {
+  static constexpr int N = 1 << LOGN;
+  static constexpr int LI = N >= 64 ? N / 64 : 1;
+  static constexpr bool kPrefetch = LOGN <= 10;
+  static constexpr int PL = kPrefetch ? LI : 1;
+  uint32_t a[PL], b[PL];
+  double so;
+  bool sum;  // two polarisations per row (wave-uniform, from the launch)
+  // global -> registers (prefetch form)
+  __device__ __forceinline__ void load(const RawRowSrc& src, int lane) {
+    if constexpr (kPrefetch) {
+      so = *src.so;
+#pragma unroll
+      for (int i = 0; i < LI; ++i) {
+        const int j = lane + 64 * i;
+        if (N >= 64 || j < N) {
+          a[i] = ld_stream(src.w0 + j);  // read once
+          if (sum) b[i] = ld_stream(src.w1 + j);
+        }
+      }
+    }
+  }
+  struct Conv {
+    double s0, o0, s1, o1;
+    bool sum;
+    __device__ __forceinline__ Conv(double so, bool sum_)
+        : s0(lane_of(so, 0)), o0(lane_of(so, 1)), s1(lane_of(so, 2)), o1(lane_of(so, 3)),
+          sum(sum_) {}
+    __device__ __forceinline__ double2 operator()(uint32_t wa, uint32_t wb) const {
+      double x = fma(raw_lo(wa), s0, o0), y = fma(raw_hi(wa), s0, o0);
+      if (sum) {
+        x = x + fma(raw_lo(wb), s1, o1);
+        y = y + fma(raw_hi(wb), s1, o1);
+      }
+      return cmk(x, y);
+    }
+  };
+  // the prefetched row as the doubles the FFT takes
+  __device__ __forceinline__ void unpack(double (&x)[PL], double (&y)[PL]) const {
+    const Conv cv(so, sum);
+#pragma unroll
+    for (int i = 0; i < PL; ++i) {
+      const double2 v = cv(a[i], sum ? b[i] : 0u);
+      x[i] = v.x;
+      y[i] = v.y;
+    }
+  }
+  // registers -> LDS (prefetch form), or global -> LDS directly: four words
+  // (eight samples) per lane and load
+  __device__ __forceinline__ void store(double2* buf, const RawRowSrc& src, int lane) const {
+    if constexpr (kPrefetch) {
+      const Conv cv(so, sum);
+#pragma unroll
+      for (int i = 0; i < LI; ++i) {
+        const int j = lane + 64 * i;
+        if (N >= 64 || j < N) buf[j] = cv(a[i], sum ? b[i] : 0u);
+      }
+    } else {
+      const Conv cv(*src.so, sum);
+      const uint4* q0 = reinterpret_cast<const uint4*>(src.w0);
+      const uint4* q1 = reinterpret_cast<const uint4*>(src.w1);
+#pragma unroll 4
+      for (int i = 0; i < LI / 4; ++i) {
+        const int j = lane + 64 * i;
+        const uint4 u = q0[j];
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (sum) v = q1[j];
+        buf[4 * j] = cv(u.x, v.x);
+        buf[4 * j + 1] = cv(u.y, v.y);
+        buf[4 * j + 2] = cv(u.z, v.z);
+        buf[4 * j + 3] = cv(u.w, v.w);
+      }
     }
   }
 };

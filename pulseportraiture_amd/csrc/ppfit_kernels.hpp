@@ -31,6 +31,14 @@ struct SpecArgs {
   double2* D;              // chunk [c][nchan][NHP] data spectra (spec cache) or null
   unsigned char* gdyn;     // WIDE kernels: [block][gdyn_stride] per-channel tables in HBM
   size_t gdyn_stride;
+  // raw rows (k_data_xspec<L, W, true>; data is null): 16-bit samples
+  // [nsub][rnpol][nchan][nbin] as packed pairs, scl / offs [nsub][rnpol][nchan].
+  // A row is polarisation rp0, plus polarisation rp1 when rsum (k_unpack's
+  // pmode 1; rp1 = rp0 otherwise)
+  const uint32_t* raw;
+  const double* scl;
+  const double* offs;
+  int rnpol, rp0, rp1, rsum;
 };
 
 // The per-channel tables a workgroup builds (Meta, the data pass's channel
@@ -853,7 +861,8 @@ __global__ void k_twiddles(double2* tw, int nbin);
 template <class Row>
 __global__ void k_model_spec(const double* model, double2* M, double* pn, int NHP, int zero_dc,
                              const double2* tw, double* M2, Row row);
-template <int LOGN, bool WIDE = false> __global__ void k_data_xspec(SpecArgs a);
+// RAW: the rows are 16-bit samples with a scale and an offset (RawWaveRow)
+template <int LOGN, bool WIDE = false, bool RAW = false> __global__ void k_data_xspec(SpecArgs a);
 template <class Row> __global__ void k_phase_shift(PhaseShiftArgs a, Row row);
 template <class Row>
 __global__ void k_rotate_rows(const double* in, const double* phase, const double* tau,

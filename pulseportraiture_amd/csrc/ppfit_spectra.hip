@@ -92,7 +92,9 @@ inline size_t xspec_dyn_lds(int nchan) {
   return (size_t)nchan * sizeof(double2) + (((size_t)nchan + 15) & ~(size_t)15);
 }
 
-template <int LOGN, bool WIDE>
+// RAW: the rows are 16-bit samples (RawWaveRow, ppfit_device.hpp); only where
+// a wave's row comes from and how it becomes the FFT's doubles differ.
+template <int LOGN, bool WIDE, bool RAW>
 __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
   using Cfg = XspecCfg<LOGN>;
   constexpr int N = Cfg::N;
@@ -125,7 +127,17 @@ __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
   const int midx = a.model_idx ? a.model_idx[s] : 0;
   const double* fr = a.freqs + (size_t)s * nchan;
   const uint8_t* mask = a.mask ? a.mask + (size_t)s * nchan : nullptr;
-  const double* drow0 = a.data + (size_t)s * nchan * (2 * N);
+  // row q of this subint, addressed by absolute subint
+  auto rowp = [&](int q) {
+    if constexpr (RAW) {
+      const size_t m0 = ((size_t)s * a.rnpol + a.rp0) * nchan + q;
+      const size_t m1 = ((size_t)s * a.rnpol + a.rp1) * nchan + q;
+      return RawRowSrc{a.raw + m0 * N, a.raw + m1 * N,
+                       ((lane & 1) ? a.offs : a.scl) + ((lane & 2) ? m1 : m0)};
+    } else {
+      return a.data + ((size_t)s * nchan + q) * (2 * N);
+    }
+  };
   double2* buf = bufs[w];
   auto active_g = [&](int q) { return q < nchan && (!mask || mask[q]); };
   // after the cmeta barrier; wave-uniform (q is), read as a scalar so that
@@ -135,9 +147,10 @@ __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
     return q < nchan && __builtin_amdgcn_readfirstlane((int)cact[q]) != 0;
   };
 
-  WaveRow<LOGN> row;
+  std::conditional_t<RAW, RawWaveRow<LOGN>, WaveRow<LOGN>> row;
+  if constexpr (RAW) row.sum = a.rsum != 0;
   bool have = active_g(w);  // the registers hold (or are loading) this wave's next row
-  if (have) row.load(drow0 + (size_t)w * 2 * N, lane);  // first row in flight
+  if (have) row.load(rowp(w), lane);  // first row in flight
   if constexpr (REGFFT) ftw[0].fill(a.tw, tid, nthr);
   else fill_pass_tw<LOGN>(twl, a.tw, tid, nthr);
   // nu_g (guess dedispersion reference) default: mean over fitted channels
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
     const int n = g * WPB + w;
     const bool act = active(n);
     if (lane == 0) s_act[w] = act;
-    if (act && !have) row.load(drow0 + (size_t)n * 2 * N, lane);
+    if (act && !have) row.load(rowp(n), lane);
     have = false;
     // template harmonics k and N - k of this row, in flight during the FFT
     // (M is shared by every subint: L2-resident)
@@ -212,17 +225,24 @@ __global__ __launch_bounds__(kBlock, 2) void k_data_xspec(SpecArgs a) {
     // spectrum pass cover it), else after the FFT
     const bool nxt = active(n + WPB);
     auto load_next = [&] {
-      if (nxt) row.load(drow0 + (size_t)(n + WPB) * 2 * N, lane);
+      if (nxt) row.load(rowp(n + WPB), lane);
     };
     constexpr bool EARLY = REGFFT && PPF_EARLY_ROW;
     if (act) {
       mload(0, m0k, m0n);
       mload(1, m1k, m1n);
-      if constexpr (REGFFT) {
+      if constexpr (REGFFT && RAW) {
+        // the packed row is consumed here: its registers are the next row's
+        // from load_next on
+        double x[16], y[16];
+        row.unpack(x, y);
+        if constexpr (EARLY) fft1024_wave(x, y, buf, ftw[0], lane, load_next);
+        else fft1024_wave(x, y, buf, ftw[0], lane);
+      } else if constexpr (REGFFT) {
         if constexpr (EARLY) fft1024_wave(row.x, row.y, buf, ftw[0], lane, load_next);
         else fft1024_wave(row.x, row.y, buf, ftw[0], lane);
       } else {
-        row.store(buf, drow0 + (size_t)n * 2 * N, lane);
+        row.store(buf, rowp(n), lane);
         fft_sync<true>();
         wave_fft<LOGN>(buf, twl, lane);
       }
@@ -837,8 +857,10 @@ __global__ __launch_bounds__(kBlock) void k_resid_chi2(ResidArgs a, const double
   template __global__ void k_rot_accum<R>(const double*, const double*, const double*,       \
                                           double2*, int, int, int, const double2*, R);
 #define PPF_INST(L)                                                                          \
-  template __global__ void k_data_xspec<L, false>(SpecArgs);                                 \
-  template __global__ void k_data_xspec<L, true>(SpecArgs);                                  \
+  template __global__ void k_data_xspec<L, false, false>(SpecArgs);                          \
+  template __global__ void k_data_xspec<L, true, false>(SpecArgs);                           \
+  template __global__ void k_data_xspec<L, false, true>(SpecArgs);                           \
+  template __global__ void k_data_xspec<L, true, true>(SpecArgs);                            \
   PPF_INST_ROW(RowPow2<L>)
 PPF_INST(5)
 PPF_INST(6)

@@ -229,6 +229,103 @@ def results_to_host_async(out, keys, stream, side):
     return _PendingHost(out, keys, stream, side)
 
 
+_RAW_TYPES = {torch.uint8: _lib.RAW_U8, torch.int16: _lib.RAW_I16, torch.float32: _lib.RAW_F32}
+
+
+class RawSubints:
+    """PSRFITS samples as fit input: raw [nsub, npol, nchan, nbin] (uint8,
+    int16 or float32) with scl / offs [nsub, npol, nchan] float64 (DAT_SCL,
+    DAT_OFFS), standing for the [nsub, nchan, nbin] values raw * scl + offs
+    of one polarisation (pmode 0: ipol), of AA + BB (pmode 1) or of the first
+    polarisation (pmode 2, Stokes I), as unpack_subints forms them.
+    Engine.fit_batch, fit_batch_streamed and FitPipeline.submit take one
+    where they take data; 16-bit samples at a power-of-two nbin are read by
+    the fit itself (ppf_fit_portrait_batch_raw), anything else is unpacked
+    first.  torch tensors or numpy arrays, on any device; rs[a:b] is a view,
+    rs[index_list] gathers subints."""
+
+    def __init__(self, raw, scl, offs, pmode=0, ipol=0):
+        raw, scl, offs = [torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+                          for x in (raw, scl, offs)]
+        for x in (raw, scl, offs):
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("RawSubints: torch tensors or numpy arrays")
+        if raw.dim() != 4:
+            raise ValueError("RawSubints: raw [nsub, npol, nchan, nbin], got %s" % (tuple(raw.shape),))
+        if raw.dtype not in _RAW_TYPES:
+            raise TypeError("RawSubints: raw %s is not uint8, int16 or float32" % raw.dtype)
+        for name, x in (("scl", scl), ("offs", offs)):
+            if x.dtype != torch.float64:
+                raise TypeError("RawSubints: %s %s is not float64" % (name, x.dtype))
+            if tuple(x.shape) != tuple(raw.shape[:3]):
+                raise ValueError("RawSubints: %s %s, raw %s" % (name, tuple(x.shape),
+                                                                  tuple(raw.shape)))
+            if x.device != raw.device:
+                raise ValueError("RawSubints: %s on %s, raw on %s" % (name, x.device, raw.device))
+        npol = int(raw.shape[1])
+        pmode, ipol = int(pmode), int(ipol)
+        if pmode not in (0, 1, 2):
+            raise ValueError("RawSubints: pmode %d outside 0..2" % pmode)
+        if pmode == 1 and npol < 2:
+            raise ValueError("RawSubints: pmode 1 sums two polarisations, npol %d" % npol)
+        if not 0 <= ipol < max(npol, 1):
+            raise ValueError("RawSubints: ipol %d with npol %d" % (ipol, npol))
+        self.raw, self.scl, self.offs, self.pmode, self.ipol = raw, scl, offs, pmode, ipol
+
+    @property
+    def shape(self):
+        n, _, nchan, nbin = self.raw.shape
+        return (int(n), int(nchan), int(nbin))
+
+    @property
+    def device(self):
+        return self.raw.device
+
+    @property
+    def nbytes(self):
+        """Bytes held: samples, scales and offsets."""
+        return sum(x.numel() * x.element_size() for x in (self.raw, self.scl, self.offs))
+
+    def __len__(self):
+        return int(self.raw.shape[0])
+
+    def is_pinned(self):
+        return all(x.is_pinned() for x in (self.raw, self.scl, self.offs))
+
+    def __getitem__(self, idx):
+        if isinstance(idx, slice):
+            if idx.step not in (None, 1):
+                raise IndexError("RawSubints: slices of step 1, or a list of subints")
+            parts = [x[idx] for x in (self.raw, self.scl, self.offs)]  # views
+        else:
+            ix = torch.as_tensor(np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx),
+                                 dtype=torch.long, device=self.device)
+            if ix.dim() != 1:
+                raise IndexError("RawSubints: a slice or a list of subint indices")
+            parts = [x.index_select(0, ix) for x in (self.raw, self.scl, self.offs)]
+        return RawSubints(*parts, pmode=self.pmode, ipol=self.ipol)
+
+    def to(self, device, non_blocking=False):
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        return RawSubints(*[x.to(device, non_blocking=non_blocking)
+                            for x in (self.raw, self.scl, self.offs)],
+                          pmode=self.pmode, ipol=self.ipol)
+
+    def unpack(self, eng, out=None):
+        """The values [nsub, nchan, nbin] as a float64 tensor on eng's device
+        (Engine.unpack_subints; out: a [nsub, 1, nchan, nbin] tensor to fill)."""
+        rs = self.to(eng.device)
+        raw, scl, offs = rs.raw, rs.scl, rs.offs
+        if rs.pmode == 0 and raw.shape[1] > 1:  # the one polarisation fitted
+            raw, scl, offs = [x[:, rs.ipol:rs.ipol + 1] for x in (raw, scl, offs)]
+        raw, scl, offs = raw.contiguous(), scl.contiguous(), offs.contiguous()
+        o = eng.unpack_subints(raw, scl, offs, pmode=rs.pmode, out=out)
+        o._keep = (raw, scl, offs)
+        return o[:, 0]
+
+
 class Engine:
     """One libppfit context on one HIP device (one per process/GPU)."""
 
@@ -357,7 +454,10 @@ class Engine:
                   eval_only=False, guess_direct=False, spec_cache=None):
         """fit_portrait_full over a batch (pptoaslib.py:928-1096).
 
-        data [nsub, nchan, nbin]; model [nmodel, nchan, nbin] (or [nchan, nbin]);
+        data [nsub, nchan, nbin], or a RawSubints: its 16-bit samples are read
+        by the data pass itself at a power-of-two nbin (no fp64 copy exists;
+        ppf_fit_portrait_batch_raw, the same results bit for bit) and unpacked
+        first otherwise; model [nmodel, nchan, nbin] (or [nchan, nbin]);
         freqs [nsub, nchan] or [nchan]; P [nsub] or scalar; init [nsub, 5] or [5].
         errs: time-domain sigma per channel; None or NaN entries are estimated
         on the device as get_noise_PS (pplib.py:2227-2253).
@@ -378,10 +478,22 @@ class Engine:
         if method not in _lib.METHODS:
             raise PPFitError("Method '%s' is not implemented." % method)
         dev = self.device
-        d = _dev_f64(data, dev)
-        if d.dim() == 2:
-            d = d.unsqueeze(0)
-        nsub, nchan, nbin = d.shape
+        rs = None
+        if isinstance(data, RawSubints):
+            rs = data.to(dev)
+            rs = RawSubints(rs.raw.contiguous(), rs.scl.contiguous(), rs.offs.contiguous(),
+                            rs.pmode, rs.ipol)
+            if rs.raw.dtype != torch.int16 or rs.raw.data_ptr() % 16 or len(rs) == 0 or \
+                    self.row_transform(rs.shape[2]) != "pow2":
+                data, rs = rs.unpack(self), None
+        if rs is not None:
+            d = None
+            nsub, nchan, nbin = rs.shape
+        else:
+            d = _dev_f64(data, dev)
+            if d.dim() == 2:
+                d = d.unsqueeze(0)
+            nsub, nchan, nbin = d.shape
         # every host-side (numpy) input goes to the device in one pinned H2D
         # copy on the context stream; device tensors are used as they are
         st = _Stager(dev, self.stream)
@@ -431,7 +543,7 @@ class Engine:
             bnd = (ctypes.c_double * 10)(*[
                 np.nan if v is None else float(v) for b in bounds for v in (list(b) + [None, None])[:2]])
         desc.bounds = ctypes.cast(bnd, ctypes.c_void_p) if bnd is not None else None
-        keep = dict(d=d, m=m, fr=fr, P=Pt, it=it, nf=nf, no=no, er=er, mk=mk, wt=wt,
+        keep = dict(d=d, rs=rs, m=m, fr=fr, P=Pt, it=it, nf=nf, no=no, er=er, mk=mk, wt=wt,
                     mi=mi, gn=gn, gt=gt, staged=getattr(st, "buf", None))
         desc.data, desc.model, desc.model_idx = _ptr(d), _ptr(m), _ptr(mi)
         desc.freqs, desc.errs, desc.chan_mask = _ptr(fr), _ptr(er), _ptr(mk)
@@ -454,8 +566,16 @@ class Engine:
                   "init_used", "fun", "cov_nosc", "grad", "hess"]:
             setattr(res, k, _ptr(out[k]))
         res.errs_out = _ptr(out["errs"])
-        self._chk(self.lib.ppf_fit_portrait_batch(self.ctx, ctypes.byref(desc),
-                                                  ctypes.byref(res)))
+        if rs is not None:
+            rd = _lib.RawSubintsDesc()
+            rd.raw_type, rd.npol = _RAW_TYPES[rs.raw.dtype], int(rs.raw.shape[1])
+            rd.pmode, rd.ipol = rs.pmode, rs.ipol
+            rd.raw, rd.scl, rd.offs = _ptr(rs.raw), _ptr(rs.scl), _ptr(rs.offs)
+            self._chk(self.lib.ppf_fit_portrait_batch_raw(self.ctx, ctypes.byref(desc),
+                                                          ctypes.byref(rd), ctypes.byref(res)))
+        else:
+            self._chk(self.lib.ppf_fit_portrait_batch(self.ctx, ctypes.byref(desc),
+                                                      ctypes.byref(res)))
         if spec_cache is not None:
             spec_cache.stored = True
         out["_keep"] = keep  # inputs must outlive the stream-ordered call
@@ -467,21 +587,30 @@ class Engine:
         not fit in HBM: chunk i + 1 is copied host -> device on a second
         stream while chunk i is fitted on the context stream (two device
         buffers).  host_data should be a pinned torch CPU tensor for full
-        PCIe rate (an unpinned one is copied synchronously).  Per-subint
+        PCIe rate (an unpinned one is copied synchronously), or a host
+        RawSubints: then the buffers hold its samples, scales and offsets
+        (no fp64 buffer is allocated) and the fits read those.  Per-subint
         arguments (leading dimension nsub) are sliced per chunk; results are
         those of one fit_batch call over all subints, concatenated on the
         device."""
         dev = self.device
-        hd = host_data if isinstance(host_data, torch.Tensor) else torch.from_numpy(
-            np.ascontiguousarray(host_data, dtype=np.float64))
-        nsub, nchan, nbin = hd.shape
+        rs = host_data if isinstance(host_data, RawSubints) else None
+        if rs is not None:
+            parts = [rs.raw, rs.scl, rs.offs]  # what a chunk's buffers hold
+            nsub = len(rs)
+        else:
+            hd = host_data if isinstance(host_data, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(host_data, dtype=np.float64))
+            parts = [hd]
+            nsub = hd.shape[0]
         chunk = max(1, min(int(chunk), nsub))
         # pageable input: each chunk is staged into one of two pinned buffers
         # on the host (a CPU copy that overlaps the previous chunk's fit),
         # then copied to the device asynchronously
-        staged = not hd.is_pinned()
-        pin = [torch.empty((chunk, nchan, nbin), dtype=torch.float64, pin_memory=True)
-               for _ in range(2)] if staged else None
+        staged = not all(p.is_pinned() for p in parts)
+        fdt = (lambda p: torch.float64) if rs is None else (lambda p: p.dtype)
+        pin = [[torch.empty((chunk,) + tuple(p.shape[1:]), dtype=fdt(p), pin_memory=True)
+                for p in parts] for _ in range(2)] if staged else None
 
         # per-subint arguments and the ndim at which they carry a subint axis
         # (a [nchan] freqs row or a [5] init row is shared, never sliced)
@@ -498,8 +627,8 @@ class Engine:
 
         comp = self.stream
         copy = torch.cuda.Stream(dev)
-        bufs = [torch.empty((chunk, nchan, nbin), dtype=torch.float64, device=dev)
-                for _ in range(2)]
+        bufs = [[torch.empty((chunk,) + tuple(p.shape[1:]), dtype=fdt(p), device=dev)
+                 for p in parts] for _ in range(2)]
         copied = [torch.cuda.Event() for _ in range(2)]
         free = [torch.cuda.Event() for _ in range(2)]
         h2d_done = [None, None]
@@ -508,16 +637,18 @@ class Engine:
         def issue(i):
             s0 = i * chunk
             n = min(chunk, nsub - s0)
-            src = hd[s0:s0 + n]
+            srcs = [p[s0:s0 + n] for p in parts]
             if staged:
                 if h2d_done[i % 2] is not None:
                     h2d_done[i % 2].synchronize()  # the pinned buffer's last H2D finished
-                pin[i % 2][:n].copy_(src)
-                src = pin[i % 2][:n]
+                for pb, src in zip(pin[i % 2], srcs):
+                    pb[:n].copy_(src)
+                srcs = [pb[:n] for pb in pin[i % 2]]
             with torch.cuda.stream(copy):
                 if i >= 2:
                     copy.wait_event(free[i % 2])  # chunk i - 2 is done with the buffer
-                bufs[i % 2][:n].copy_(src, non_blocking=True)
+                for db, src in zip(bufs[i % 2], srcs):
+                    db[:n].copy_(src, non_blocking=True)
                 copied[i % 2].record(copy)
                 if staged:
                     h2d_done[i % 2] = torch.cuda.Event()
@@ -535,7 +666,9 @@ class Engine:
             for k in per_sub:
                 if k in kwi:
                     kwi[k] = part(k, kwi[k], s0, s1)
-            r = self.fit_batch(bufs[i % 2][:s1 - s0], model, part("freqs", freqs, s0, s1),
+            cur = [db[:s1 - s0] for db in bufs[i % 2]]
+            dat = cur[0] if rs is None else RawSubints(*cur, pmode=rs.pmode, ipol=rs.ipol)
+            r = self.fit_batch(dat, model, part("freqs", freqs, s0, s1),
                                part("P", P, s0, s1), part("init", init, s0, s1), fit_flags,
                                **kwi)
             free[i % 2].record(comp)
@@ -1349,7 +1482,8 @@ class FitPipeline:
     pieces still run -- so the caller's host work on piece i (get_TOAs' TOA
     records and .tim text) overlaps the device work of pieces i+1, ...
 
-    Host-resident pieces (numpy or CPU tensors) are staged through two
+    Host-resident pieces (numpy, CPU tensors or a host RawSubints, whose
+    samples, scales and offsets travel as they are) are staged through two
     pinned buffers and copied to two device buffers on a second stream, the
     copy of piece i+1 overlapping the fit of piece i (as fit_batch_streamed).
     submit(tag, data, model, ...) takes fit_batch's arguments; collect()
@@ -1359,20 +1493,22 @@ class FitPipeline:
         self.eng, self.keys = eng, keys
         self.pending = collections.deque()
         self.copy = self.side = None
-        self.slots = [None, None]  # (pinned, device buffer, h2d event, free event)
+        self.slots = [None, None]  # (pinned, device buffer (bytes), h2d event, free event)
         self.models = {}
         self.k = 0
 
     def __len__(self):
         return len(self.pending)
 
-    def _stage(self, host):
-        """Host piece -> device tensor, through slot k % 2."""
+    def _stage(self, parts):
+        """Host tensors of one piece -> device tensors, through slot k % 2:
+        each side one byte buffer, a part at a 256-byte boundary."""
         eng = self.eng
-        hd = host if isinstance(host, torch.Tensor) else torch.from_numpy(
-            np.ascontiguousarray(host, dtype=np.float64))
-        hd = hd.to(torch.float64)
-        n = hd.numel()
+        parts = [p.contiguous() for p in parts]
+        offs, n = [], 0
+        for p in parts:
+            offs.append(n)
+            n += (p.numel() * p.element_size() + 255) // 256 * 256
         i = self.k % 2
         self.k += 1
         if self.copy is None:
@@ -1383,27 +1519,34 @@ class FitPipeline:
                 for ev in slot[2:]:
                     if ev is not None:
                         ev.synchronize()
-            slot = [None, torch.empty(n, dtype=torch.float64, device=eng.device), None, None]
+            slot = [None, torch.empty(n, dtype=torch.uint8, device=eng.device), None, None]
             self.slots[i] = slot
-        if hd.is_pinned():
-            src = hd.reshape(-1)
+
+        def view(buf, p, o):
+            return buf[o:o + p.numel() * p.element_size()].view(p.dtype).view(p.shape)
+
+        if all(p.is_pinned() for p in parts):
+            srcs = parts
         else:
             if slot[2] is not None:
                 slot[2].synchronize()  # the pinned buffer's previous H2D is done
             if slot[0] is None or slot[0].numel() < n:
-                slot[0] = torch.empty(n, dtype=torch.float64, pin_memory=True)
-            slot[0][:n].copy_(hd.reshape(-1))
-            src = slot[0][:n]
+                slot[0] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            srcs = [view(slot[0], p, o) for p, o in zip(parts, offs)]
+            for src, p in zip(srcs, parts):
+                src.copy_(p)
         dbuf, free = slot[1], slot[3]
+        dst = [view(dbuf, p, o) for p, o in zip(parts, offs)]
         with torch.cuda.stream(self.copy):
             if free is not None:
                 self.copy.wait_event(free)  # the fit that read the device buffer is done
-            dbuf[:n].copy_(src, non_blocking=True)
+            for d, src in zip(dst, srcs):
+                d.copy_(src, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.copy)
         slot[2] = ev
         eng.stream.wait_event(ev)
-        return dbuf[:n].view(hd.shape), i
+        return dst, i
 
     def submit(self, tag, data, model, freqs, P, init, fit_flags, **kw):
         if isinstance(model, np.ndarray):  # one device copy per template array
@@ -1412,8 +1555,14 @@ class FitPipeline:
                 hit = self.models[id(model)] = (model, _dev_f64(model, self.eng.device))
             model = hit[1]
         slot = None
-        if not isinstance(data, torch.Tensor) or data.device.type == "cpu":
-            data, slot = self._stage(data)
+        if isinstance(data, RawSubints):
+            if data.device.type == "cpu":
+                dst, slot = self._stage([data.raw, data.scl, data.offs])
+                data = RawSubints(*dst, pmode=data.pmode, ipol=data.ipol)
+        elif not isinstance(data, torch.Tensor) or data.device.type == "cpu":
+            hd = data if isinstance(data, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(data, dtype=np.float64))
+            (data,), slot = self._stage([hd.to(torch.float64)])
         out = self.eng.fit_batch(data, model, freqs, P, init, fit_flags, **kw)
         if slot is not None:
             ev = torch.cuda.Event()

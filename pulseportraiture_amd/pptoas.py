@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import archive as _arch
-from .engine import FitPipeline, get_engine
+from .engine import FitPipeline, RawSubints, get_engine
 from .mjd import MJD, add_days_parts, epoch_parts
 from .pplib import (DataBunch, F0_fact, phase_transform, gen_gaussian_portraits_device,
                     guess_fit_freq, scattering_alpha, scattering_times, weighted_mean, write_TOAs,
@@ -194,9 +194,21 @@ class GetTOAs:
     "all" -- every rank assembles the same TOAs.  ``read_bytes_max`` bounds
     the bytes of one subint-range read of an archive that materialises its
     data (PSRFITS, .npz): a rank's shard is read and fitted in pieces of at
-    most that size (registered in-memory archives are views, read whole)."""
+    most that size (registered in-memory archives are views, read whole).
+    ``raw_samples = True`` lets the fits of a PSRFITS archive read its 16-bit
+    samples themselves (engine.RawSubints): no fp64 copy of a read piece is
+    made, the pieces are sized by the samples' bytes, and the TOAs are those
+    of the default path.  It applies when nothing has to process the data
+    first (no dedispersion, baseline removal or tscrunch) and the noise is
+    the fit's own (pplib.default_noise_method "PS"); otherwise the default
+    path runs.  load_data's SNRs (Profile::snr()) still need fp64 profiles:
+    they are taken from one scratch tensor of at most ``raw_snr_bytes``
+    (default 1 GiB), refilled piece by piece."""
     gather_to = "root"
     read_bytes_max = 8 << 30
+    raw_samples = False
+    raw_snr_bytes = 1 << 30
+    read_raw_pieces = 0  # read pieces whose fits took the samples (diagnostic)
     # device-resident subints of one call are fitted in pieces of these
     # fractions (at least pipeline_min_subints in all), each piece's TOA
     # records built while the next runs; pipeline_depth fits in flight
@@ -985,6 +997,9 @@ class GetTOAs:
         if not getattr(job.arch, "owns_reads", True):
             return [subs]
         per = 8 * int(data.npol) * int(data.nchan) * int(data.nbin)
+        if len(subs):  # raw samples: the bytes one subint of them holds
+            one = self._read_raw(job, int(subs[0]), int(subs[0]) + 1)
+            per = one.nbytes if one is not None else per
         span = max(1, int(self.read_bytes_max) // per)
         out, i = [], 0
         while i < len(subs):
@@ -993,21 +1008,54 @@ class GetTOAs:
             i = j
         return out
 
+    def _read_raw(self, job, lo, hi):
+        """Subints lo:hi as RawSubints when raw_samples applies, else None."""
+        from . import pplib
+        if not self.raw_samples or pplib.default_noise_method != "PS":
+            return None
+        read_raw = getattr(job.arch, "read_raw", None)
+        return None if read_raw is None else read_raw(lo, hi)
+
+    def _raw_snrs(self, rs):
+        """profile_snr of every profile of rs (all polarisations kept by its
+        pscrunch mode), [n, npo, nchan] numpy: the values are unpacked into
+        one scratch tensor of at most raw_snr_bytes, a piece at a time."""
+        import torch
+        eng = get_engine()
+        n, npol, nchan, nbin = rs.raw.shape
+        npo = 1 if rs.pmode else int(npol)
+        step = max(1, min(n, int(self.raw_snr_bytes) // (8 * npo * int(nchan) * int(nbin))))
+        scratch = torch.empty((step, npo, nchan, nbin), dtype=torch.float64, device=eng.device)
+        out = np.empty((n, npo, nchan))
+        for a in range(0, n, step):
+            b = min(n, a + step)
+            piece = eng.unpack_subints(rs.raw[a:b], rs.scl[a:b], rs.offs[a:b], rs.pmode,
+                                       out=scratch[:b - a])
+            out[a:b] = eng.profile_snr(piece).cpu().numpy()  # waits: the scratch is free again
+        return out
+
     def _read(self, job, subs, fit_scat):
         """Read the subint range of subs (one read piece): (first subint,
-        [n, nchan, nbin] numpy or device view, noise rows or None).  A
-        PSRFITS archive's deferred SNRs (Profile::snr(), pplib.py:2762-2770)
-        come from the data just read, then those subints' nu_fit and
-        scattering guess."""
+        [n, nchan, nbin] numpy or device view -- or the piece's RawSubints
+        under raw_samples --, noise rows or None).  A PSRFITS archive's
+        deferred SNRs (Profile::snr(), pplib.py:2762-2770) come from the data
+        just read, then those subints' nu_fit and scattering guess."""
         data = job.data
         s_lo, s_hi = int(subs[0]), int(subs[-1]) + 1
-        full = job.arch.read(s_lo, s_hi)  # [s_hi - s_lo, npol, nchan, nbin], numpy or device
+        rs = self._read_raw(job, s_lo, s_hi)
+        if rs is not None:
+            self.read_raw_pieces += 1
+            full, sub = None, rs
+        else:
+            full = job.arch.read(s_lo, s_hi)  # [s_hi - s_lo, npol, nchan, nbin], numpy or device
+            sub = full[:, 0]
         if data.get("snr_deferred"):
-            data.SNRs[s_lo:s_hi] = get_engine().profile_snr(full).cpu().numpy()
+            data.SNRs[s_lo:s_hi] = self._raw_snrs(rs) if rs is not None else \
+                get_engine().profile_snr(full).cpu().numpy()
             self._nu_fit_and_tau(data, subs, job.wn, job.allok, job.nu_fit_tuple, fit_scat,
                                  job.nu_fits_a, job.init, job.guess_tau, job.uniform["freqs"])
         ns = data.get("noise_stds")
-        return s_lo, full[:, 0], None if ns is None else np.asarray(ns)[:, 0]
+        return s_lo, sub, None if ns is None else np.asarray(ns)[:, 0]
 
     def _pipe_split(self, subs, sub):
         """Pipeline pieces of one read piece: host-resident subints in pieces
@@ -1015,7 +1063,7 @@ class GetTOAs:
         resident ones in shrinking fractions (pipeline_fracs) so that the
         host work after the last piece is small."""
         n = len(subs)
-        if _arch._is_tensor(sub) and sub.device.type != "cpu":
+        if (_arch._is_tensor(sub) or isinstance(sub, RawSubints)) and sub.device.type != "cpu":
             if n < self.pipeline_min_subints:
                 return [subs]
             cuts = np.cumsum([0.0] + list(self.pipeline_fracs))

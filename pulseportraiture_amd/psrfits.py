@@ -363,6 +363,21 @@ class PSRFITSSource:
         sub._keep = (rd, scl, offs)
         return sub
 
+    def read_raw(self, lo, hi, engine=None):
+        """Subints lo:hi as the file stores them: an engine.RawSubints on the
+        device (samples, DAT_SCL, DAT_OFFS) carrying this source's pscrunch
+        mode, for fits that read the samples themselves.  Unscrunched files of
+        several polarisations stand for their first, as the fits of read()'s
+        [:, 0] do."""
+        from .engine import RawSubints, get_engine
+        import torch
+        dev = (engine or get_engine()).device
+        rd = torch.from_numpy(self.f.raw(lo, hi - lo)).to(dev)
+        scl = torch.from_numpy(np.ascontiguousarray(self.m["scl"][lo:hi], dtype=np.float64)).to(dev)
+        offs = torch.from_numpy(np.ascontiguousarray(self.m["offs"][lo:hi],
+                                                     dtype=np.float64)).to(dev)
+        return RawSubints(rd, scl, offs, pmode=self.pmode, ipol=0)
+
     def close(self):
         self.f.close()
 
