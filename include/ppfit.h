@@ -31,6 +31,9 @@
  *                              arch.fscrunch() in pplib.make_constant_portrait
  *                              (pplib.py:958-994) and the profiles psradd -P
  *                              aligns on (ppalign.py:21-38)
+ *   ppf_scrunch_subints     <- arch.fscrunch() / bscrunch() of load_data
+ *                              (pplib.py:2714) and pam -f / -b, from fp64
+ *                              values or 16-bit samples (a stand-in, unpinned)
  *   ppf_irfft_rows          <- numpy.fft.irfft (final step of ppalign.py:210-213)
  *   ppf_noise_rows          <- pplib.get_noise_PS(chans=True)  pplib.py:2227-2253
  *   ppf_noise_fit_rows      <- pplib.get_noise_fit(chans=True) pplib.py:2255-2287
@@ -575,6 +578,38 @@ int ppf_rotate_accumulate_spec(ppf_ctx* ctx, int32_t nsub, int32_t nchan,
 int ppf_rotate_fscrunch(ppf_ctx* ctx, int32_t nunit, int32_t nchan, int32_t nbin,
                         const double* data, const double* phase, const double* weight,
                         double* prof);
+
+/* Frequency- and bin-scrunch subints: the stand-in for `pam -f / -b`, NOT
+ * pinned against pam.  For every subint s, kept polarisation p and group g of
+ * f adjacent channels (n in g: channels g f .. g f + f - 1),
+ *   W            = sum_{n in g} w[s][n]
+ *   y            = irfft(sum_{n in g, w != 0} w[s][n] rfft(x[s][p][n])_k e^{2 pi i k phase[s][n]},
+ *                        nbin) / W
+ *   out[s][p][g][j] = (1/b) sum_{i < b} y[j b + i]        wout[s][g] = W
+ * A group with W = 0 gives zeros and weight 0; a sample under weight 0 never
+ * enters a sum (a NaN there is harmless).  weights and phase [nsub][nchan],
+ * out [nsub][npol][nchan/f][nbin/b], wout [nsub][nchan/f]; device pointers.
+ * Exactly one of data and raw is given:
+ *   data  fp64 [nsub][npol][nchan][nbin] -- viewed as [nsub npol nchan/f][f][nbin]
+ *         it is what ppf_rotate_fscrunch sums, by the same kernels;
+ *   raw   16-bit PSRFITS samples (ppf_raw_subints above), read as they are:
+ *         no fp64 copy of the data exists, and every output is bit for bit
+ *         that of ppf_unpack_subints followed by this call on its values.
+ *         pmode 1 and 2 keep one polarisation (npol = 1); pmode 0 keeps
+ *         polarisation ipol (npol = 1) or, with ipol < 0, every stored one
+ *         (npol = raw->npol).  PPF_ERR_UNSUPPORTED unless raw_type is
+ *         PPFITS_RAW_I16 and nbin a power of two in [64, 8192]: unpack those
+ *         first, in bounded chunks (Engine.scrunch_subints does).
+ * The bins are averaged as they stand, with no compensating rotation: bin j
+ * of the output is centred (b - 1) / (2 nbin) of a turn later than bin j b
+ * of the input.  PPF_ERR_INVALID: a null pointer, f not dividing nchan, b
+ * not dividing nbin; PPF_ERR_UNSUPPORTED: nbin / b < 16, nbin outside
+ * [16, 8192].  A group's output is bitwise the same whatever else shares the
+ * call and under any workspace limit (the channel order of
+ * ppf_rotate_fscrunch; units are chunked, never split).                     */
+int ppf_scrunch_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                        const double* data, const ppf_raw_subints* raw, const double* weights,
+                        const double* phase, int32_t f, int32_t b, double* out, double* wout);
 
 /* Gaussian-component template rows (gen_gaussian_portrait, pplib.py:853-930,
  * as read_model calls it, pplib.py:2873-2959): out[r][:] at freqs[r] for

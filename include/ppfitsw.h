@@ -21,6 +21,7 @@
 #ifndef PPFITSW_H
 #define PPFITSW_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -65,6 +66,22 @@ int ppfw_write_subints(ppfw_file* f, int32_t isub0, int32_t n, const int16_t* ra
 int ppfw_close(ppfw_file* f);
 
 const char* ppfw_error(const ppfw_file* f);
+
+/* Set DAT_WTS[isub[i]][ichan[i]] = wts[i], i < n, of the existing fold-mode
+ * PSRFITS file at path, in place: the stand-in for `paz -m`.  Only the bytes
+ * of those cells change (each is written in the column's own type, E or D);
+ * the header, the history, the polyco and every sample stay as they were.
+ * Any fold-mode file ppfits.h reads can be patched, this writer's own
+ * included.  Everything is checked before the first byte is written:
+ *   PPFITS_ERR_FORMAT  not FITS, OBS_MODE other than PSR / CAL, no SUBINT
+ *                      table or DAT_WTS column, or a SUBINT HDU that carries
+ *                      CHECKSUM / DATASUM -- such a file is REFUSED, not
+ *                      re-summed (this writer emits neither keyword);
+ *   PPFITS_ERR_RANGE   a subint or channel outside the table;
+ * and the file is then untouched.  err (may be NULL) receives the reason,
+ * at most errlen bytes with the terminator.                                 */
+int ppfw_patch_weights(const char* path, int32_t n, const int32_t* isub, const int32_t* ichan,
+                       const double* wts, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

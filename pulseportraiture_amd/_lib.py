@@ -120,6 +120,9 @@ EXPORTS = {
                                     ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_rotate_fscrunch": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_scrunch_subints": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                             ctypes.c_int32, _dp, ctypes.POINTER(RawSubintsDesc), _dp, _dp,
+                             ctypes.c_int32, ctypes.c_int32, _dp, _dp], ctypes.c_int),
     "ppf_spec_nhp": ([ctypes.c_int32], ctypes.c_int32),
     "ppf_row_transform": ([ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)],
                           ctypes.c_int),

@@ -572,8 +572,12 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False, tscrun
     device, unless the archive already holds it."""
     if isinstance(filename, dict):
         return normalize(filename)
-    if fscrunch:
-        raise NotImplementedError("load_data(fscrunch=True) is not on the fitting path")
+    if fscrunch:  # arch.fscrunch() (pplib.py:2714): every channel into one
+        b = load_data(filename, state=state, dedisperse=dedisperse, dededisperse=dededisperse,
+                      tscrunch=tscrunch, pscrunch=pscrunch, rm_baseline=rm_baseline,
+                      flux_prof=flux_prof, refresh_arch=refresh_arch, return_arch=return_arch,
+                      quiet=quiet, get_SNRs=False, host=False)
+        return scrunch(b, nchan=1)
     a = open_archive(filename, dedisperse=dedisperse, dededisperse=dededisperse,
                      tscrunch=tscrunch, pscrunch=pscrunch, rm_baseline=rm_baseline, quiet=quiet)
     b = DataBunch(**dict(a.meta))
@@ -608,6 +612,100 @@ def tscrunch(b, period_at=None):
     for k in ("ok_isubs", "ok_ichans", "masks"):
         out.pop(k, None)
     return normalize(out, b.filename)
+
+
+_tscrunch_bunch = tscrunch  # scrunch's own tscrunch argument hides the function
+
+
+def scrunch(bunch_or_name, nchan=None, nbin=None, tscrunch=False, **load_kw):
+    """A load_data bunch at lower resolution: the stand-in for `pam --setnchn
+    nchan --setnbin nbin [-T]` (Engine.scrunch_subints; a defined stand-in,
+    NOT pinned against pam).  bunch_or_name: a load_data bunch,
+    or an archive load_data reads (loaded as stored, with load_kw).  nchan
+    must divide the archive's nchan and nbin its nbin (ValueError otherwise);
+    None keeps the resolution.  tscrunch first averages every subint into one
+    (archive.tscrunch; partial tscrunch is not offered).
+
+    fscrunch: every group of f = nchan_in / nchan adjacent channels becomes
+    sum_n w_n rot(x_n, phase_n) / W with W = sum_n w_n, per subint and
+    polarisation; the group's weight is W and its frequency sum_n w_n nu_n / W
+    (the plain mean of the group's frequencies when W = 0, where the profile
+    is zeros).  phase is 0 for an archive stored dedispersed; otherwise it is
+    dedispersion_phases about the group's own frequency, so a group is
+    dedispersed within itself and the result stays "not dedispersed" between
+    groups (dmc is unchanged).
+
+    bscrunch: the plain mean of every b = nbin_in / nbin adjacent bins, with
+    no compensating rotation: output bin j averages input bins j b .. j b +
+    b - 1, so against the input's phase axis the output's bin centres lie
+    (b - 1) / (2 nbin_in) of a turn later than the centres get_bin_centers
+    gives them (`phases` of the result).  Every profile moves alike: relative
+    TOAs and DMs are not affected, an absolute phase is, by that offset.
+
+    noise_stds and SNRs are re-estimated on the device from the scrunched
+    profiles, as after tscrunch.  subints come back on the host.
+
+    A PSRFITS file whose load processes nothing (rm_baseline=False or a
+    baseline already removed, no dedispersion, no tscrunch -- what
+    pplib.scrunch_archive asks for) is scrunched from its stored samples
+    (Archive.read_raw, engine.RawSubints): no fp64 copy of the archive exists,
+    and the result is bit for bit that of the loaded fp64 values.  Any other
+    request loads the archive as fp64 values first (load_data)."""
+    from .engine import get_engine
+    data = None
+    if isinstance(bunch_or_name, dict):
+        b = normalize(bunch_or_name, bunch_or_name.get("filename", "archive"))
+        if tscrunch:
+            b = _tscrunch_bunch(b)
+    else:
+        load_kw.setdefault("quiet", True)
+        # nothing to process (no rotation, baseline removal or tscrunch) in a
+        # PSRFITS file: its samples as they are stored, with no fp64 copy
+        if not tscrunch and set(load_kw) <= {"dedisperse", "dededisperse", "pscrunch",
+                                             "rm_baseline", "quiet"}:
+            a = open_archive(bunch_or_name, **load_kw)
+            data = a.read_raw()
+            if data is not None:
+                b = normalize(DataBunch(**dict(a.meta)), a.meta.get("filename", "archive"),
+                              subints=False)
+        if data is None:
+            b = load_data(bunch_or_name, tscrunch=tscrunch, get_SNRs=False, host=False, **load_kw)
+    if data is None:
+        data = b.subints
+    nchan = b.nchan if nchan is None else int(nchan)
+    nbin = b.nbin if nbin is None else int(nbin)
+    if nchan < 1 or b.nchan % nchan:
+        raise ValueError("scrunch: nchan=%d does not divide %d channels" % (nchan, b.nchan))
+    if nbin < 1 or b.nbin % nbin:
+        raise ValueError("scrunch: nbin=%d does not divide %d bins" % (nbin, b.nbin))
+    f, nb = b.nchan // nchan, b.nbin // nbin
+    w = np.asarray(b.weights, dtype=np.float64)
+    wg = w.reshape(b.nsub, nchan, f)
+    fg = np.asarray(b.freqs, dtype=np.float64).reshape(b.nsub, nchan, f)
+    W, Wnu = np.zeros((b.nsub, nchan)), np.zeros((b.nsub, nchan))
+    for n in range(f):  # in channel order, as the device sums W
+        W += wg[:, :, n]
+        Wnu += wg[:, :, n] * fg[:, :, n]
+    gfreqs = np.where(W != 0.0, Wnu / np.where(W != 0.0, W, 1.0), fg.mean(axis=2))
+    if int(b.get("dmc", 0)):
+        phase = np.zeros_like(w)
+    else:
+        phase = dedispersion_phases(b.freqs, b.Ps, b.DM, np.repeat(gfreqs, f, axis=1))
+    eng = get_engine()
+    # a raw archive that is not pscrunched keeps every stored polarisation
+    sub, wout = eng.scrunch_subints(data, w, phase, f, nb,
+                                    all_pols=not _is_tensor(data) and
+                                    not isinstance(data, np.ndarray) and data.pmode == 0)
+    out = DataBunch(**{k: v for k, v in b.items()
+                       if k not in ("ok_isubs", "ok_ichans", "masks", "epoch_parts", "phases",
+                                    "subints", "_stack", "snr_deferred")})
+    out.freqs = gfreqs
+    out.weights = wout.cpu().numpy()
+    out.noise_stds = _noise_rows(eng, sub.reshape(-1, nbin)).reshape(
+        b.nsub, b.npol, nchan).cpu().numpy()
+    out.SNRs = Archive.snrs(sub)
+    out.subints = sub.cpu().numpy()
+    return normalize(out, b.get("filename", "archive"))
 
 
 ARRAY_KEYS = ["subints", "freqs", "weights", "Ps", "SNRs", "doppler_factors",

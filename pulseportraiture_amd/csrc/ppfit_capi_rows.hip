@@ -48,6 +48,117 @@ int launch_pack(ppf_ctx* ctx, size_t rows, int nbin, const double* data, int16_t
   });
 }
 
+// What ppf_scrunch_subints adds to ppf_rotate_fscrunch's sum: the weights and
+// phases [nsub][ngroup nchan] to lay out per unit, 16-bit rows in place of
+// fp64 ones, and the division by W with the mean of b adjacent bins.
+struct ScrunchExtra {
+  const FsRaw* raw;       // null: fp64 rows
+  const double* weights;
+  const double* phase;
+  int npo, ngroup, b;
+  double* wout;           // [nsub][ngroup]
+};
+
+// prof[u] = irfft(sum_n weight[u][n] rfft(row(u, n)) e^{2 pi i k phase[u][n]}) for
+// nunit units of nchan channels; with sx, phase and weight come from it and
+// prof [nunit][nbin / b] is the scrunched profile.
+int fscrunch_units(ppf_ctx* ctx, int64_t nunit, int nchan, int nbin, int logN,
+                   const double* data, const double* phase, const double* weight, double* prof,
+                   const ScrunchExtra* sx) {
+  const double2* tw;
+  if (int r = twiddles(ctx, nbin, &tw)) return r;
+  const int NH = nbin / 2 + 1;
+  // slices of kFsSlice channels whatever the call holds: a unit's profile
+  // is summed in the same order alone or among others
+  const int nslice = (nchan + kFsSlice - 1) / kFsSlice;
+  // per unit: the slices' partial spectra, then the unit's spectrum; units in
+  // chunks under the workspace limit (and one launch's grid)
+  WsPlan ws;
+  const int wPart = ws.array((size_t)nslice * NH * sizeof(double2));
+  const int wSpec = ws.array((size_t)NH * sizeof(double2));
+  // scrunch: the unit's weights and phases, W, and its profile at nbin bins
+  const int wWx = sx ? ws.array((size_t)nchan * sizeof(double)) : -1;
+  const int wPhx = sx ? ws.array((size_t)nchan * sizeof(double)) : -1;
+  const int wW = sx ? ws.array(sizeof(double)) : -1;
+  const int wProf = sx ? ws.array((size_t)nbin * sizeof(double)) : -1;
+  // slack: 256 bytes of alignment per array
+  ws.lay_out(nunit, ctx->ws_limit, sx ? 1536 : 512, (int64_t)0x7fffffff / nslice);
+  if (int r = hold_workspace(ctx, ws)) return r;
+  const int64_t chunk = ws.chunk;
+  double2* partial = ws.at<double2>(wPart);
+  double2* spec = ws.at<double2>(wSpec);
+  const int nyq = (nbin & 1) ? -1 : nbin / 2;
+  const bool wave = logN == 10;  // nbin 2048: the register FFT (2.6x the LDS kernel, DESIGN §12)
+  const int nbo = sx ? nbin / sx->b : nbin;
+  for (int64_t u0 = 0; u0 < nunit; u0 += chunk) {
+    const int nu = (int)std::min<int64_t>(chunk, nunit - u0);
+    const double* d = data ? data + (size_t)u0 * nchan * nbin : nullptr;
+    const double* ph = phase ? phase + (size_t)u0 * nchan : nullptr;
+    const double* w = weight ? weight + (size_t)u0 * nchan : nullptr;
+    double* rows = sx ? ws.at<double>(wProf) : prof + (size_t)u0 * nbin;  // the irfft's output
+    if (sx) {
+      double* wx = ws.at<double>(wWx);
+      double* phx = ws.at<double>(wPhx);
+      if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+            hipLaunchKernelGGL(k_scrunch_meta, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0,
+                               ctx->stream, sx->weights, sx->phase, u0, nu, sx->npo, sx->ngroup,
+                               nchan, wx, phx, ws.at<double>(wW), sx->wout);
+          }))
+        return r;
+      ph = phx;
+      w = wx;
+    }
+    const unsigned grid = (unsigned)nu * (unsigned)nslice;
+    const size_t count = (size_t)nu * NH;
+    if (sx && sx->raw) {  // 16-bit rows: the power-of-two kernels' raw twins
+      FsRaw fr = *sx->raw;
+      fr.unit0 = u0;
+      if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+            if (wave)
+              hipLaunchKernelGGL(k_fscrunch_w_raw, dim3(grid), dim3(256), 0, ctx->stream, fr, ph,
+                                 w, partial, nchan, nslice, tw);
+            else
+              LOGN_SWITCH(logN, hipLaunchKernelGGL(k_fscrunch_raw<LG>, dim3(grid), dim3(kBlock),
+                                                   0, ctx->stream, fr, ph, w, partial, nchan,
+                                                   nslice, tw));
+          }))
+        return r;
+    } else if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          if (logN < 0)
+            hipLaunchKernelGGL(k_fscrunch_gen, dim3(grid), dim3(kBlock),
+                               RowAny::lds(nbin, kLdsRow), ctx->stream, d, ph, w, partial, nchan,
+                               nslice, tw, RowAny{nbin});
+          else if (wave)
+            hipLaunchKernelGGL(k_fscrunch_w, dim3(grid), dim3(256), 0, ctx->stream, d, ph, w,
+                               partial, nchan, nslice, tw);
+          else
+            LOGN_SWITCH(logN, hipLaunchKernelGGL(k_fscrunch<LG>, dim3(grid), dim3(kBlock), 0,
+                                                 ctx->stream, d, ph, w, partial, nchan, nslice,
+                                                 tw));
+        }))
+      return r;
+    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          hipLaunchKernelGGL(k_fscrunch_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256),
+                             0, ctx->stream, partial, spec, nslice, NH, nyq, count);
+        }))
+      return r;
+    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+          launch_irfft_rows(ctx->stream, logN, nbin, nu, spec, rows, tw);
+        }))
+      return r;
+    if (sx) {
+      const size_t nout = (size_t)nu * nbo;
+      if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
+            hipLaunchKernelGGL(k_scrunch_mean, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0,
+                               ctx->stream, rows, ws.at<double>(wW), prof + (size_t)u0 * nbo, nbin,
+                               sx->b, nout);
+          }))
+        return r;
+    }
+  }
+  return PPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -583,56 +694,55 @@ int ppf_rotate_fscrunch(ppf_ctx* ctx, int32_t nunit, int32_t nchan, int32_t nbin
     HIPCHK(ctx, hipMemsetAsync(prof, 0, (size_t)nunit * nbin * sizeof(double), ctx->stream));
     return PPF_OK;
   }
-  const double2* tw;
-  if (int r = twiddles(ctx, nbin, &tw)) return r;
-  const int NH = nbin / 2 + 1;
-  // slices of kFsSlice channels whatever the call holds: a unit's profile
-  // is summed in the same order alone or among others
-  const int nslice = (nchan + kFsSlice - 1) / kFsSlice;
-  // per unit: the slices' partial spectra, then the unit's spectrum; units in
-  // chunks under the workspace limit (and one launch's grid)
-  WsPlan ws;
-  const int wPart = ws.array((size_t)nslice * NH * sizeof(double2));
-  const int wSpec = ws.array((size_t)NH * sizeof(double2));
-  ws.lay_out(nunit, ctx->ws_limit, 512, (int64_t)0x7fffffff / nslice);
-  if (int r = hold_workspace(ctx, ws)) return r;
-  const int64_t chunk = ws.chunk;
-  double2* partial = ws.at<double2>(wPart);
-  double2* spec = ws.at<double2>(wSpec);
-  const int nyq = (nbin & 1) ? -1 : nbin / 2;
-  const bool wave = logN == 10;  // nbin 2048: the register FFT (2.6x the LDS kernel, DESIGN §12)
-  for (int64_t u0 = 0; u0 < nunit; u0 += chunk) {
-    const int nu = (int)std::min<int64_t>(chunk, nunit - u0);
-    const double* d = data + (size_t)u0 * nchan * nbin;
-    const double* ph = phase + (size_t)u0 * nchan;
-    const double* w = weight + (size_t)u0 * nchan;
-    const unsigned grid = (unsigned)nu * (unsigned)nslice;
-    const size_t count = (size_t)nu * NH;
-    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
-          if (logN < 0)
-            hipLaunchKernelGGL(k_fscrunch_gen, dim3(grid), dim3(kBlock),
-                               RowAny::lds(nbin, kLdsRow), ctx->stream, d, ph, w, partial, nchan,
-                               nslice, tw, RowAny{nbin});
-          else if (wave)
-            hipLaunchKernelGGL(k_fscrunch_w, dim3(grid), dim3(256), 0, ctx->stream, d, ph, w,
-                               partial, nchan, nslice, tw);
-          else
-            LOGN_SWITCH(logN, hipLaunchKernelGGL(k_fscrunch<LG>, dim3(grid), dim3(kBlock), 0,
-                                                 ctx->stream, d, ph, w, partial, nchan, nslice,
-                                                 tw));
-        }))
-      return r;
-    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
-          hipLaunchKernelGGL(k_fscrunch_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256),
-                             0, ctx->stream, partial, spec, nslice, NH, nyq, count);
-        }))
-      return r;
-    if (int r = timed(ctx, PPF_K_FSCRUNCH, [&] {
-          launch_irfft_rows(ctx->stream, logN, nbin, nu, spec, prof + (size_t)u0 * nbin, tw);
-        }))
-      return r;
+  return fscrunch_units(ctx, nunit, nchan, nbin, logN, data, phase, weight, prof, nullptr);
+}
+
+int ppf_scrunch_subints(ppf_ctx* ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                        const double* data, const ppf_raw_subints* raw, const double* weights,
+                        const double* phase, int32_t f, int32_t b, double* out, double* wout) {
+  if (!ctx || !weights || !phase || !out || !wout || (data == nullptr) == (raw == nullptr))
+    return fail(ctx, PPF_ERR_INVALID, "null argument (data or raw, not both)");
+  if (raw && (!raw->raw || !raw->scl || !raw->offs))
+    return fail(ctx, PPF_ERR_INVALID, "null argument");
+  if (nsub <= 0) return PPF_OK;
+  if (npol <= 0 || nchan <= 0 || nbin <= 0)
+    return fail(ctx, PPF_ERR_INVALID, "bad shape (%d, %d, %d)", npol, nchan, nbin);
+  if (f < 1 || nchan % f) return fail(ctx, PPF_ERR_INVALID, "f=%d does not divide nchan=%d", f, nchan);
+  if (b < 1 || nbin % b) return fail(ctx, PPF_ERR_INVALID, "b=%d does not divide nbin=%d", b, nbin);
+  if (nbin / b < 16)
+    return fail(ctx, PPF_ERR_UNSUPPORTED, "nbin / b = %d: fewer than 16 bins", nbin / b);
+  int logN;
+  if (int r = check_nbin_any(ctx, nbin, &logN)) return r;
+  const int ngroup = nchan / f;
+  if ((int64_t)nsub * npol * ngroup > 0x7fffffffLL)
+    return fail(ctx, PPF_ERR_INVALID, "%lld profiles in one call", (long long)nsub * npol * ngroup);
+  FsRaw fr{};
+  if (raw) {
+    if (raw->raw_type != PPFITS_RAW_I16 || logN < 5)
+      return fail(ctx, PPF_ERR_UNSUPPORTED,
+                  "raw rows: 16-bit samples at a power-of-two nbin in [64, 8192] (unpack first)");
+    const bool all = raw->pmode == 0 && raw->ipol < 0;
+    if (raw->npol <= 0 || raw->pmode < 0 || raw->pmode > 2 || (raw->pmode == 1 && raw->npol < 2) ||
+        (raw->pmode == 0 && raw->ipol >= raw->npol) || npol != (all ? raw->npol : 1))
+      return fail(ctx, PPF_ERR_INVALID, "pmode %d, ipol %d with %d stored and %d kept polarisations",
+                  raw->pmode, raw->ipol, raw->npol, npol);
+    if (reinterpret_cast<uintptr_t>(raw->raw) % 4)  // rows are read as packed pairs
+      return fail(ctx, PPF_ERR_INVALID, "raw is not 4-byte aligned");
+    fr.raw = static_cast<const uint32_t*>(raw->raw);
+    fr.scl = raw->scl;
+    fr.offs = raw->offs;
+    fr.rnpol = raw->npol;
+    fr.rsum = raw->pmode == 1;
+    fr.rp0 = raw->pmode == 0 ? (all ? -1 : raw->ipol) : 0;
+    fr.rp1 = fr.rsum ? 1 : fr.rp0;
+    fr.npo = npol;
+    fr.ngroup = ngroup;
+    fr.nchan_all = nchan;
   }
-  return PPF_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const ScrunchExtra sx{raw ? &fr : nullptr, weights, phase, npol, ngroup, b, wout};
+  return fscrunch_units(ctx, (int64_t)nsub * npol * ngroup, f, nbin, logN, data, nullptr, nullptr,
+                        out, &sx);
 }
 
 int ppf_gaussian_portraits(ppf_ctx* ctx, int32_t nrow, int32_t nbin, int32_t ngauss,

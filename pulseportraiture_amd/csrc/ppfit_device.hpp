@@ -647,6 +647,9 @@ struct RawWaveRow {
     __device__ __forceinline__ Conv(double so, bool sum_)
         : s0(lane_of(so, 0)), o0(lane_of(so, 1)), s1(lane_of(so, 2)), o1(lane_of(so, 3)),
           sum(sum_) {}
+    // the same from the four values themselves (a workgroup per row)
+    __device__ __forceinline__ Conv(double s0_, double o0_, double s1_, double o1_, bool sum_)
+        : s0(s0_), o0(o0_), s1(s1_), o1(o1_), sum(sum_) {}
     __device__ __forceinline__ double2 operator()(uint32_t wa, uint32_t wb) const {
       double x = fma(raw_lo(wa), s0, o0), y = fma(raw_hi(wa), s0, o0);
       if (sum) {

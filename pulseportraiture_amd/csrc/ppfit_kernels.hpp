@@ -921,6 +921,28 @@ __global__ void k_fscrunch_gen(const double* data, const double* phase, const do
                                RowAny row);
 __global__ void k_fscrunch_reduce(const double2* partial, double2* spec, int nslice, int NH,
                                   int nyq, size_t count);
+// ppf_scrunch_subints from 16-bit samples: unit unit0 + u = (s npo + q) ngroup
+// + g is kept polarisation q and channel group g of subint s; its channel n
+// is stored channel g f + n (f: the kernels' nchan)
+struct FsRaw {
+  const uint32_t* raw;  // [nsub][rnpol][nchan_all][nbin] as packed pairs
+  const double* scl;    // [nsub][rnpol][nchan_all]
+  const double* offs;
+  int rnpol;            // polarisations stored
+  int rp0, rp1, rsum;   // a row is polarisation rp0 (< 0: the unit's own q), plus rp1 when rsum
+  int npo, ngroup, nchan_all;
+  int64_t unit0;        // the launch's first unit
+};
+template <int LOGN>
+__global__ void k_fscrunch_raw(FsRaw src, const double* phase, const double* weight,
+                               double2* partial, int nchan, int nslice, const double2* tw);
+__global__ void k_fscrunch_w_raw(FsRaw src, const double* phase, const double* weight,
+                                 double2* partial, int nchan, int nslice, const double2* tw);
+__global__ void k_scrunch_meta(const double* weights, const double* phase, int64_t unit0, int nu,
+                               int npo, int ngroup, int f, double* wx, double* phx, double* Wx,
+                               double* wout);
+__global__ void k_scrunch_mean(const double* prof, const double* Wx, double* out, int nbin, int b,
+                               size_t count);
 // ppf_fake_subints / ppf_pack_subints (ppfit_fake.hip)
 struct FakeArgs {
   const double2* M;     // model spectra [nchan][NHP]

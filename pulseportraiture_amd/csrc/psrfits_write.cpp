@@ -10,7 +10,9 @@
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -150,6 +152,109 @@ Header table_header(const char* extname, const std::vector<Col>& cols, size_t nr
 
 std::string field(const char* s, size_t cap) {  // a desc string, NUL-terminated or full
   return std::string(s, strnlen(s, cap));
+}
+
+// ---- ppfw_patch_weights: where DAT_WTS lies in an existing file -----------
+std::string trim(const std::string& s) {
+  const size_t a = s.find_first_not_of(' '), b = s.find_last_not_of(' ');
+  return a == std::string::npos ? std::string() : s.substr(a, b - a + 1);
+}
+
+// value text of a card: a quoted string without its quotes, or the token
+// before any comment
+std::string card_value(const char* c) {
+  const std::string v(c + 10, kCard - 10);
+  const size_t i = v.find_first_not_of(' ');
+  if (i == std::string::npos) return "";
+  if (v[i] == '\'') {
+    const size_t j = v.find('\'', i + 1);
+    return trim(v.substr(i + 1, j == std::string::npos ? std::string::npos : j - i - 1));
+  }
+  const size_t slash = v.find('/', i);
+  return trim(v.substr(i, slash == std::string::npos ? std::string::npos : slash - i));
+}
+
+struct WtsPlace {
+  size_t data_off = 0, row_bytes = 0, nrows = 0, col_off = 0;
+  long nchan = 0;
+  char type = 0;  // 'E' or 'D'
+};
+
+// Walk the HDUs of fp to SUBINT and find its DAT_WTS column; "" or the reason
+// the file cannot be patched.
+std::string find_wts(FILE* fp, WtsPlace* out) {
+  std::vector<char> blk(kBlock);
+  size_t off = 0;
+  for (int ih = 0;; ++ih) {
+    std::map<std::string, std::string> kv;
+    size_t hdr = 0;
+    for (bool end = false; !end;) {
+      if (fseeko(fp, (off_t)(off + hdr), SEEK_SET) != 0 || fread(blk.data(), 1, kBlock, fp) != kBlock)
+        return ih > 0 && hdr == 0 ? "no SUBINT table (not a fold-mode PSRFITS file)"
+                                  : "truncated FITS header";
+      hdr += kBlock;
+      for (size_t c = 0; c < kBlock && !end; c += kCard) {
+        const char* card = blk.data() + c;
+        const std::string key = trim(std::string(card, 8));
+        if (key == "END") end = true;
+        else if (ih == 0 && hdr == kBlock && c == 0 && key != "SIMPLE") return "not a FITS file";
+        else if (card[8] == '=' && !key.empty()) kv[key] = card_value(card);
+      }
+    }
+    auto num = [&](const std::string& k, long long dflt) {
+      auto it = kv.find(k);
+      return it == kv.end() || it->second.empty() ? dflt : atoll(it->second.c_str());
+    };
+    if (ih == 0) {
+      const std::string mode = kv.count("OBS_MODE") ? kv["OBS_MODE"] : "";
+      if (mode != "PSR" && mode != "CAL")
+        return "OBS_MODE '" + mode + "' is not fold mode (PSR or CAL)";
+    }
+    const long long naxis = num("NAXIS", 0);
+    size_t n = naxis > 0 ? 1 : 0;
+    for (long long a = 1; a <= naxis; ++a) n *= (size_t)num("NAXIS" + std::to_string(a), 0);
+    const size_t bitpix = (size_t)std::llabs(num("BITPIX", 8));
+    const size_t bytes = bitpix / 8 * (size_t)num("GCOUNT", 1) * ((size_t)num("PCOUNT", 0) + n);
+    if (kv.count("EXTNAME") && kv["EXTNAME"] == "SUBINT") {
+      if (kv.count("CHECKSUM") || kv.count("DATASUM"))
+        return "SUBINT carries CHECKSUM / DATASUM, which a patch would invalidate";
+      out->data_off = off + hdr;
+      out->row_bytes = (size_t)num("NAXIS1", 0);
+      out->nrows = (size_t)num("NAXIS2", 0);
+      if (num("NBIN", 0) < 2) return "SUBINT NBIN < 2: not fold mode";
+      size_t co = 0;
+      bool found = false;
+      for (long long i = 1, nf = num("TFIELDS", 0); i <= nf; ++i) {
+        const std::string form = kv["TFORM" + std::to_string(i)];
+        size_t p = 0;
+        while (p < form.size() && form[p] >= '0' && form[p] <= '9') ++p;
+        if (p >= form.size()) return "bad TFORM '" + form + "'";
+        long rep = p ? atol(form.substr(0, p).c_str()) : 1;
+        const char t = form[p];
+        size_t w;
+        switch (t) {
+          case 'L': case 'B': case 'A': w = 1; break;
+          case 'X': w = 1; rep = (rep + 7) / 8; break;
+          case 'I': w = 2; break;
+          case 'J': case 'E': w = 4; break;
+          case 'K': case 'D': case 'C': case 'P': w = 8; break;
+          case 'M': case 'Q': w = 16; break;
+          default: return "unsupported TFORM '" + form + "'";
+        }
+        if (kv["TTYPE" + std::to_string(i)] == "DAT_WTS") {
+          if (t != 'E' && t != 'D') return "DAT_WTS is neither E nor D";
+          out->col_off = co;
+          out->nchan = rep;
+          out->type = t;
+          found = true;
+        }
+        co += w * (size_t)rep;
+      }
+      if (co != out->row_bytes) return "column widths != NAXIS1 in SUBINT";
+      return found ? "" : "SUBINT has no DAT_WTS column";
+    }
+    off += hdr + (bytes + kBlock - 1) / kBlock * kBlock;
+  }
 }
 
 }  // namespace
@@ -364,6 +469,37 @@ int ppfw_close(ppfw_file* f) {
   f->fp = nullptr;
   const int rc = f->status;
   delete f;
+  return rc;
+}
+
+int ppfw_patch_weights(const char* path, int32_t n, const int32_t* isub, const int32_t* ichan,
+                       const double* wts, char* err, size_t errlen) {
+  auto fail = [&](int code, const std::string& msg) {
+    if (err && errlen) snprintf(err, errlen, "%s", msg.c_str());
+    return code;
+  };
+  if (!path || n < 0 || (n && (!isub || !ichan || !wts))) return fail(PPFITS_ERR_MISSING, "null argument");
+  FILE* fp = fopen(path, "r+b");
+  if (!fp) return fail(PPFITS_ERR_IO, std::string("cannot open ") + path + ": " + strerror(errno));
+  WtsPlace w;
+  const std::string why = find_wts(fp, &w);
+  int rc = PPFITS_OK;
+  if (!why.empty()) rc = fail(PPFITS_ERR_FORMAT, std::string(path) + ": " + why);
+  // every cell is checked before the first byte is written
+  for (int32_t i = 0; rc == PPFITS_OK && i < n; ++i)
+    if (isub[i] < 0 || (size_t)isub[i] >= w.nrows || ichan[i] < 0 || ichan[i] >= w.nchan)
+      rc = fail(PPFITS_ERR_RANGE, "cell (" + std::to_string(isub[i]) + ", " + std::to_string(ichan[i]) +
+                                      ") outside " + std::to_string(w.nrows) + " subints x " +
+                                      std::to_string(w.nchan) + " channels");
+  const size_t width = w.type == 'D' ? 8 : 4;
+  for (int32_t i = 0; rc == PPFITS_OK && i < n; ++i) {
+    uint8_t b[8];
+    if (w.type == 'D') put_f64(b, wts[i]); else put_f32(b, wts[i]);
+    const size_t at = w.data_off + (size_t)isub[i] * w.row_bytes + w.col_off + (size_t)ichan[i] * width;
+    if (fseeko(fp, (off_t)at, SEEK_SET) != 0 || fwrite(b, 1, width, fp) != width)
+      rc = fail(PPFITS_ERR_IO, "DAT_WTS write failed");
+  }
+  if (fclose(fp) != 0 && rc == PPFITS_OK) rc = fail(PPFITS_ERR_IO, "close failed");
   return rc;
 }
 

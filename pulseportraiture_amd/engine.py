@@ -1299,6 +1299,81 @@ class Engine:
         out._keep = (d, ph, w)
         return out
 
+    # values of one unpacked chunk of scrunch_subints (raw input the kernels
+    # do not read themselves): at most this many bytes of fp64 at a time
+    SCRUNCH_UNPACK_BYTES = 256 << 20
+
+    def scrunch_subints(self, data, weights, phase, f=1, b=1, all_pols=False):
+        """Frequency- and bin-scrunch subints (ppf_scrunch_subints, the
+        stand-in for pam -f / -b): every group of f adjacent channels becomes
+        their weighted, rotated sum divided by the group's weight W, every b
+        adjacent bins their mean.  data: float64 [nsub, npol, nchan, nbin], or
+        a RawSubints -- the polarisation(s) it stands for, or with
+        all_pols=True (pmode 0) every stored one; weights and phase [nsub,
+        nchan].  Returns (out [nsub, npol, nchan/f, nbin/b], wout [nsub,
+        nchan/f]) float64 on the device.  16-bit samples at a power-of-two
+        nbin in [64, 8192] are read by the kernels themselves, bit for bit as
+        unpack_subints followed by this call; other raw input is unpacked
+        first, SCRUNCH_UNPACK_BYTES of values at a time.  A group's output
+        does not depend on what else shares the call (bitwise)."""
+        dev = self.device
+        f, b = int(f), int(b)
+        rs = data if isinstance(data, RawSubints) else None
+        if rs is not None:
+            rs = rs.to(dev)
+            if all_pols and rs.pmode != 0:
+                raise PPFitError("scrunch_subints: all_pols with pmode %d" % rs.pmode)
+            nsub, nchan, nbin = rs.shape
+            npol = int(rs.raw.shape[1]) if all_pols else 1
+            d = None
+        else:
+            d = _dev_f64(data, dev)
+            if d.dim() != 4:
+                raise PPFitError("scrunch_subints: data [nsub, npol, nchan, nbin]")
+            nsub, npol, nchan, nbin = d.shape
+        w = _dev_f64(weights, dev).reshape(nsub, nchan).contiguous()
+        ph = _dev_f64(phase, dev).reshape(nsub, nchan).contiguous()
+        # shapes the entry point refuses have no output shape to allocate
+        ok = f >= 1 and b >= 1 and nchan % f == 0 and nbin % b == 0
+        ng, nbo = (nchan // f, nbin // b) if ok else (1, 1)
+        out = torch.zeros((nsub, npol, ng, nbo), dtype=torch.float64, device=dev)
+        wout = torch.zeros((nsub, ng), dtype=torch.float64, device=dev)
+        if ok and (nsub == 0 or npol == 0 or nchan == 0 or nbin == 0):
+            return out, wout
+
+        def call(a0, a1, dd, rd):
+            self._chk(self.lib.ppf_scrunch_subints(
+                self.ctx, a1 - a0, npol, nchan, nbin, _ptr(dd), rd, _ptr(w[a0:a1]),
+                _ptr(ph[a0:a1]), f, b, _ptr(out[a0:a1]), _ptr(wout[a0:a1])))
+
+        if rs is None:
+            call(0, nsub, d, None)
+            out._keep = (d, w, ph)
+            return out, wout
+        raw, scl, offs = rs.raw.contiguous(), rs.scl.contiguous(), rs.offs.contiguous()
+        # the rows the kernels read themselves: what ppf_scrunch_subints takes
+        direct = raw.dtype == torch.int16 and 16 <= nbin <= 8192 and \
+            self.row_transform(nbin) == "pow2"
+        if direct or not ok:
+            rd = _lib.RawSubintsDesc()
+            rd.raw_type, rd.npol, rd.pmode = _RAW_TYPES[raw.dtype], int(raw.shape[1]), rs.pmode
+            rd.ipol = -1 if all_pols else rs.ipol
+            rd.raw, rd.scl, rd.offs = _ptr(raw), _ptr(scl), _ptr(offs)
+            call(0, nsub, None, ctypes.byref(rd))
+            out._keep = (raw, scl, offs, w, ph)
+            return out, wout
+        if rs.pmode == 0 and not all_pols and raw.shape[1] > 1:  # the one polarisation kept
+            raw, scl, offs = [x[:, rs.ipol:rs.ipol + 1].contiguous() for x in (raw, scl, offs)]
+        step = max(1, self.SCRUNCH_UNPACK_BYTES // max(1, npol * nchan * nbin * 8))
+        buf = torch.empty((min(step, nsub), npol, nchan, nbin), dtype=torch.float64, device=dev)
+        for a0 in range(0, nsub, step):
+            a1 = min(nsub, a0 + step)
+            self.unpack_subints(raw[a0:a1], scl[a0:a1], offs[a0:a1], pmode=rs.pmode,
+                                out=buf[:a1 - a0])
+            call(a0, a1, buf, None)
+        out._keep = (raw, scl, offs, w, ph, buf)
+        return out, wout
+
     def spec_cache(self, nsub, nchan, nbin):
         """An empty data-spectrum cache for fit_batch(spec_cache=...) and
         rotate_accumulate_spec: nsub * nchan * NHP complex spectra (NHP =
@@ -1435,7 +1510,7 @@ for _name in ("fit_batch", "phase_shift_batch", "phase_tau_batch", "rotate_rows"
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "noise_fit_rows",
               "find_kc_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "rotate_fscrunch", "spec_cache",
-              "rotate_accumulate_spec",
+              "rotate_accumulate_spec", "scrunch_subints",
               "synth", "pack_subints", "fake_subints"):
     setattr(Engine, _name, _on_engine_stream(getattr(Engine, _name)))
 del _name

@@ -1436,6 +1436,20 @@ def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None, quiet=
         print("\nUnloaded %s.\n" % outfile)
 
 
+def scrunch_archive(datafile, outfile, nchan=None, nbin=None, tscrunch=False, quiet=False):
+    """Write datafile at lower resolution as the PSRFITS file outfile: the
+    stand-in for `pam --setnchn nchan --setnbin nbin [-T] -e ...`, not pinned
+    against pam.  The data are read as stored (no baseline removed),
+    scrunched by archive.scrunch -- see there for the group frequencies,
+    weights and phases and for the bin-centre offset of the bscrunch -- and
+    written by unload_new_archive with the scrunched frequencies and weights,
+    in the dedispersion state the input is stored in.  Returns outfile."""
+    from . import archive as _archive
+    b = _archive.scrunch(datafile, nchan=nchan, nbin=nbin, tscrunch=tscrunch, rm_baseline=False)
+    unload_new_archive(b.subints, b, outfile, DM=b.DM, dmc=int(b.dmc), quiet=quiet)
+    return outfile
+
+
 def scrunched_profile(bunch):
     """The T-, P- and F-scrunched profile [nbin] of a load_data bunch loaded as
     stored (pscrunch=True; subints on the host or the device): per subint the

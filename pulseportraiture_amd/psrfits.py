@@ -115,12 +115,37 @@ def load_library():
     lib.ppfw_close.restype = ctypes.c_int
     lib.ppfw_error.argtypes = [vp]
     lib.ppfw_error.restype = ctypes.c_char_p
+    lib.ppfw_patch_weights.argtypes = [ctypes.c_char_p, ctypes.c_int32, dp, dp, dp,
+                                       ctypes.c_char_p, ctypes.c_size_t]
+    lib.ppfw_patch_weights.restype = ctypes.c_int
     _lib = lib
     return lib
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def patch_weights(path, isubs, ichans, weights):
+    """Set DAT_WTS[isub][ichan] of the fold-mode PSRFITS file at path, in
+    place (ppfw_patch_weights): nothing else of the file changes.  isubs,
+    ichans and weights broadcast against each other.  A bad index, a file
+    that is not fold mode or one that carries a SUBINT checksum raises
+    PSRFITSError and leaves the file untouched."""
+    lib = load_library()
+    i, c, w = np.broadcast_arrays(np.asarray(isubs, dtype=np.int64),
+                                  np.asarray(ichans, dtype=np.int64),
+                                  np.asarray(weights, dtype=np.float64))
+    for a in (i, c):
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise PSRFITSError("%s: index outside int32" % path)
+    i = np.ascontiguousarray(i.ravel(), dtype=np.int32)
+    c = np.ascontiguousarray(c.ravel(), dtype=np.int32)
+    w = np.ascontiguousarray(w.ravel())
+    err = ctypes.create_string_buffer(512)
+    rc = lib.ppfw_patch_weights(os.fsencode(path), int(i.size), _p(i), _p(c), _p(w), err, 512)
+    if rc != 0:
+        raise PSRFITSError(err.value.decode(errors="replace") or "%s: error %d" % (path, rc))
 
 
 class PSRFITSFile:
