@@ -57,6 +57,10 @@
  *                              ppf_gauss_eval is its objective)
  *   ppf_gauss_fit_join_batch <- the same with join_params (metafile portraits;
  *                              ppf_gauss_eval_join is its objective)
+ *   ppf_powlaw_fit_rows     <- pplib.fit_powlaw                pplib.py:1763-1802
+ *                              (lmfit's leastsq, batched over rows)
+ *   ppf_line_fit_rows       <- np.polyfit in pplib.fit_DM_to_freq_resids
+ *                              pplib.py:1804-1840
  *   ppf_gauss_bank          <- ppgauss.GaussianSelector (ppgauss.py:374-640,
  *                              a person at a plot): the matched-filter bank
  *                              of pplib.auto_gaussian_profiles
@@ -716,6 +720,54 @@ int ppf_gauss_fit_join_batch(ppf_ctx* ctx, int32_t nport, int32_t nchan, int32_t
                              const int32_t* join_of, const double* dm_coef, double ftol,
                              double xtol, int32_t max_nfev, double* params, double* param_errs,
                              double* cov, double* chi2, int32_t* info);
+
+/* ---------------------------------------------------------------------- */
+/* Fits across the channels of a row (ppfit_chanfit.hip): one wave per row, */
+/* the whole fit inside one launch, no workspace.  1 <= n <= 16384 and      */
+/* nrow >= 1 (PPF_ERR_INVALID otherwise).  A row's results are bitwise the  */
+/* same whatever else shares the call.  Both are timed under PPF_K_GAUSS.   */
+/* ---------------------------------------------------------------------- */
+
+/* status of a row that cannot be fitted: fewer than 3 usable points, or a
+ * usable point with a non-finite value (y; x in the line fit), nu <= 0 or
+ * nu_ref <= 0.  Its results are NaN; the other rows are not disturbed.    */
+#define PPF_CHANFIT_UNUSABLE -3
+
+/* ppf_powlaw_fit_rows: pplib.fit_powlaw per row -- the model A (nu /
+ * nu_ref)^alpha with the residual (y - model) / errs of fit_powlaw_function
+ * (pplib.py:1204-1217), which the reference hands to lmfit's leastsq without
+ * bounds.  y, errs, freqs [nrow][n]; nu_ref [nrow]; init [nrow][2] = A,
+ * alpha.  A point whose errs is <= 0, NaN or infinite is left out: that is
+ * how a zapped channel is passed.  The power is exp(alpha ln(nu / nu_ref))
+ * in fp64.
+ *   Levenberg-Marquardt with the analytic Jacobian under the rules of
+ * ppf_gauss_fit_batch: the step from the 2 x 2 normal equations (J^T J +
+ * lambda D^2) d = -J^T r with MINPACK's column scaling D, accepted by the
+ * gain ratio; MINPACK's ftol / xtol tests (leastsq's defaults are
+ * 1.49012e-8; pass them); max_nfev evaluations at most (0: 2000 * 3).
+ *   out [nrow][6] = A, A_err, alpha, alpha_err, cov(A, alpha), chi2: errors
+ * and covariance are lmfit's with scale_covar, inv(J^T J) chi2 / dof (zeros
+ * when J^T J is singular).  info [nrow][4] = {status, evaluations made, dof
+ * = n_used - 2, n_used}; status is PPF_GAUSS_FTOL / XTOL / BOTH (converged),
+ * PPF_GAUSS_MAXFEV, PPF_GAUSS_SINGULAR, PPF_GAUSS_NONFINITE (the residual at
+ * init is not finite) or PPF_CHANFIT_UNUSABLE.                             */
+int ppf_powlaw_fit_rows(ppf_ctx* ctx, int32_t nrow, int32_t n, const double* y,
+                        const double* errs, const double* freqs, const double* nu_ref,
+                        const double* init, double ftol, double xtol, int32_t max_nfev,
+                        double* out, int32_t* info);
+
+/* ppf_line_fit_rows: np.polyfit(x, y, 1, w=w, cov=True) per row in closed
+ * form, as pplib.fit_DM_to_freq_resids uses it (pplib.py:1804-1840): a and b
+ * minimise sum (w_i (y_i - a x_i - b))^2.  x, y, w [nrow][n]; points with w
+ * <= 0 or non-finite w are left out.  x and y are centred on their
+ * w^2-weighted means before the slope is formed.
+ *   out [nrow][8] = a, b, var(a), var(b), cov(a, b), sum (w r)^2, n_used,
+ * status: the covariance of the normal equations times sum (w r)^2 / (n_used
+ * - 2) (numpy >= 1.16; older ones divided by n - 4).  status is 0,
+ * PPF_CHANFIT_UNUSABLE, or PPF_GAUSS_SINGULAR when every usable x is the
+ * same; the first six entries of such a row are NaN.                       */
+int ppf_line_fit_rows(ppf_ctx* ctx, int32_t nrow, int32_t n, const double* x, const double* y,
+                      const double* w, double* out);
 
 /* ppf_gauss_bank: the matched-filter bank of the automatic component search
  * (pplib.auto_gaussian_profiles).  For profile p, width w and bin j the

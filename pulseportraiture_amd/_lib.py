@@ -33,6 +33,11 @@ PPF_SELFTEST_N = 10
 GAUSS_STATUS = {1: "converged: ftol", 2: "converged: xtol", 3: "converged: ftol and xtol",
                 5: "evaluation cap reached", -1: "singular normal equations",
                 -2: "non-finite residual"}
+# ppf_powlaw_fit_rows / ppf_line_fit_rows: a row that cannot be fitted
+PPF_CHANFIT_UNUSABLE = -3
+CHANFIT_STATUS = dict(GAUSS_STATUS)
+CHANFIT_STATUS.update({0: "ok", -3: "fewer than 3 usable points, or a non-finite value"})
+LEASTSQ_TOL = 1.49012e-8  # scipy.optimize.leastsq's default ftol and xtol
 # ppf_set_option ids (include/ppfit.h)
 OPTIONS = {"scat_graph": 0, "scat_split": 1, "scat_tail": 2, "fuse_moments": 3, "guess_wave": 4,
            "hbm_tables": 5, "post_wave": 6, "row_fft": 7}
@@ -189,6 +194,11 @@ EXPORTS = {
                                   _dp, _dp, _dp, _dp, _dp], ctypes.c_int),
     "ppf_gauss_bank": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
                         _dp, ctypes.c_void_p, _dp, _dp, _dp], ctypes.c_int),
+    "ppf_powlaw_fit_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                             _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, _dp, _dp],
+                            ctypes.c_int),
+    "ppf_line_fit_rows": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp],
+                          ctypes.c_int),
     "ppf_synth_portraits": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                              ctypes.c_int32, _dp, _dp, ctypes.c_double,
                              ctypes.c_uint64, ctypes.c_int64, _dp], ctypes.c_int),

@@ -27,9 +27,9 @@ SOURCES = ["ppfit_lib.hip"]
 DEPS = ["ppfit_lib.hip", "ppfit_spectra.hip", "ppfit_fit.hip", "ppfit_taylor.hip", "ppfit_tnc.hip",
         "ppfit_ncg.hip", "ppfit_models.hip", "ppfit_generic.hip", "ppfit_noisefit.hip", "ppfit_fscrunch.hip", "ppfit_fake.hip", "ppfit_pca.hip",
         "ppfit_gram.hip",
-        "ppfit_gauss.hip", "ppfit_gbank.hip", "ppfit_swt.hip", "ppfit_nbscat.hip",
+        "ppfit_gauss.hip", "ppfit_gbank.hip", "ppfit_swt.hip", "ppfit_nbscat.hip", "ppfit_chanfit.hip",
         "ppfit_capi.hip", "ppfit_capi_fit.hip", "ppfit_capi_rows.hip", "ppfit_capi_pca.hip",
-        "ppfit_capi_swt.hip", "ppfit_capi_gauss.hip", "ppfit_host.hpp", "ppfit_wsplan.hpp",
+        "ppfit_capi_swt.hip", "ppfit_capi_gauss.hip", "ppfit_capi_chanfit.hip", "ppfit_host.hpp", "ppfit_wsplan.hpp",
         "ppfit_kernels.hpp", "ppfit_device.hpp", "ppfit_rowfft.hpp", "ppfit_smoothfft.hpp",
         "ppfit_vthread.hpp"]
 OUT = os.path.join(HERE, "libppfit.so")

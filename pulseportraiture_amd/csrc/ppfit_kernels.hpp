@@ -86,6 +86,19 @@ struct NbScatArgs {
   int* nfev;               // [nprof]
 };
 
+// k_powlaw_fit (ppfit_chanfit.hip): one power-law fit across the channels of a row
+struct PowlawArgs {
+  int nrow, n, cap;        // cap: evaluations at most
+  double ftol, xtol;
+  const double* y;         // [nrow][n]
+  const double* errs;      // [nrow][n]; <= 0 or non-finite leaves the point out
+  const double* freqs;     // [nrow][n]
+  const double* nu_ref;    // [nrow]
+  const double* init;      // [nrow][2] = A, alpha
+  double* out;             // [nrow][6]
+  int* info;               // [nrow][4]
+};
+
 // Taylor-moment cross-spectrum (phase-family fits, see ppfit_taylor.hip):
 // kMT moments T_m = sum_k v_k^m W_k per channel, v_k = k / N in [0, 1]; an
 // evaluation at per-channel offset y = 2 pi N delta uses terms m < kMTerm and
@@ -892,6 +905,10 @@ __global__ void k_vpow(double2* vp, int nbin, int rows);
 // NJ: 64-harmonic register slots a lane holds (64 NJ >= nbin / 2); 0: the
 // rows stay in memory (nbin > 2048)
 template <int NJ> __global__ void k_nbscat(NbScatArgs a);
+// fits across channels (ppfit_chanfit.hip)
+template <int NJ> __global__ void k_powlaw_fit(PowlawArgs a);
+__global__ void k_line_fit(int nrow, int n, const double* x, const double* y, const double* w,
+                           double* out);
 // get_noise_fit / find_kc (ppfit_noisefit.hip)
 template <class Row>
 __global__ void k_noise_fit_rows(const double* in, double fact, double* noise, int* kc_out,

@@ -1231,6 +1231,53 @@ class Engine:
         kc._keep = (p2, e)
         return kc.reshape(p.shape[:-1]), idx.reshape(p.shape[:-1])
 
+    def powlaw_fit_rows(self, y, errs, freqs, nu_ref, init, ftol=_lib.LEASTSQ_TOL,
+                        xtol=_lib.LEASTSQ_TOL, max_nfev=0):
+        """pplib.fit_powlaw per row (ppf_powlaw_fit_rows): y, errs, freqs
+        [nrow, n] (freqs and errs may be [n]), nu_ref scalar or [nrow], init [2]
+        or [nrow, 2] = A, alpha.  Points with errs <= 0 or non-finite are left
+        out.  Returns (out [nrow, 6] float64 = A, A_err, alpha, alpha_err,
+        cov(A, alpha), chi2; info [nrow, 4] int32 = status, evaluations, dof,
+        n_used), device tensors."""
+        dev = self.device
+        yy = _dev_f64(y, dev)
+        if yy.dim() == 1:
+            yy = yy.unsqueeze(0)
+        if yy.dim() != 2:
+            raise PPFitError("powlaw_fit_rows: y must be [nrow, n]")
+        nrow, n = yy.shape
+        ee = _bcast_dev(_dev_f64(errs, dev), nrow, n, dev)
+        ff = _bcast_dev(_dev_f64(freqs, dev), nrow, n, dev)
+        nr = _bcast_dev(_dev_f64(nu_ref, dev), nrow, 1, dev).reshape(nrow)
+        x0 = _bcast_dev(_dev_f64(init, dev), nrow, 2, dev)
+        out = torch.empty(nrow, 6, dtype=torch.float64, device=dev)
+        info = torch.empty(nrow, 4, dtype=torch.int32, device=dev)
+        self._chk(self.lib.ppf_powlaw_fit_rows(self.ctx, nrow, n, _ptr(yy), _ptr(ee), _ptr(ff),
+                                               _ptr(nr), _ptr(x0), float(ftol), float(xtol),
+                                               int(max_nfev), _ptr(out), _ptr(info)))
+        out._keep = (yy, ee, ff, nr, x0)
+        return out, info
+
+    def line_fit_rows(self, x, y, w):
+        """np.polyfit(x, y, 1, w=w, cov=True) per row (ppf_line_fit_rows): x, y,
+        w [nrow, n] (x and w may be [n]); points with w <= 0 or non-finite are
+        left out.  Returns out [nrow, 8] float64 = a, b, var(a), var(b),
+        cov(a, b), sum (w r)^2, n_used, status (a device tensor)."""
+        dev = self.device
+        yy = _dev_f64(y, dev)
+        if yy.dim() == 1:
+            yy = yy.unsqueeze(0)
+        if yy.dim() != 2:
+            raise PPFitError("line_fit_rows: y must be [nrow, n]")
+        nrow, n = yy.shape
+        xx = _bcast_dev(_dev_f64(x, dev), nrow, n, dev)
+        ww = _bcast_dev(_dev_f64(w, dev), nrow, n, dev)
+        out = torch.empty(nrow, 8, dtype=torch.float64, device=dev)
+        self._chk(self.lib.ppf_line_fit_rows(self.ctx, nrow, n, _ptr(xx), _ptr(yy), _ptr(ww),
+                                             _ptr(out)))
+        out._keep = (xx, yy, ww)
+        return out
+
     def resid_chi2_rows(self, data, phase, model, scale, errs, dof, tau=None,
                         model_row=None):
         """Per-row reduced chi2 of rotate(data, phase) - scale * scatter(model, tau)
@@ -1508,7 +1555,7 @@ for _name in ("fit_batch", "phase_shift_batch", "phase_tau_batch", "rotate_rows"
               "instrumental_response_rows",
               "response_table", "tscrunch",
               "remove_baseline", "profile_snr", "irfft_rows", "noise_rows", "noise_fit_rows",
-              "find_kc_rows", "resid_chi2_rows",
+              "find_kc_rows", "powlaw_fit_rows", "line_fit_rows", "resid_chi2_rows",
               "scatter_rotate_rows", "rotate_accumulate", "rotate_fscrunch", "spec_cache",
               "rotate_accumulate_spec", "scrunch_subints",
               "synth", "pack_subints", "fake_subints"):

@@ -766,6 +766,146 @@ def weighted_mean(data, errs=1.0):
     return (data[i] * w).sum() / w.sum(), w.sum() ** -0.5
 
 
+def get_WRMS(data, errs=1.0):
+    """The weighted root-mean-square about the weighted mean, weights
+    errs**-2 over the points with errs > 0 (pplib.py:711-725)."""
+    if hasattr(errs, "is_integer"):
+        errs = np.ones(len(data))
+    data, errs = np.asarray(data), np.asarray(errs)
+    i = np.where(errs > 0.0)[0]
+    w_mean = weighted_mean(data, errs)[0]
+    w = errs[i] ** -2.0
+    return (((data[i] - w_mean) ** 2.0 * w).sum() / w.sum()) ** 0.5
+
+
+def powlaw(nu, nu_ref, A, alpha):
+    """A (nu / nu_ref)**alpha (pplib.py:1048-1052)."""
+    return A * (nu / nu_ref) ** alpha
+
+
+def powlaw_integral(nu2, nu1, nu_ref, A, alpha):
+    """The integral of powlaw from nu1 to nu2 (pplib.py:1054-1066)."""
+    alpha = np.float64(alpha)
+    if alpha == -1.0:
+        return A * nu_ref * np.log(nu2 / nu1)
+    C = A * (nu_ref ** -alpha) / (1 + alpha)
+    return C * (nu2 ** (1 + alpha) - nu1 ** (1 + alpha))
+
+
+def powlaw_freqs(lo, hi, N, alpha, mid=False):
+    """The N + 1 edges between lo and hi of N channels that hold equal flux
+    under a power law of index alpha; mid=True returns the N channel centres
+    instead (pplib.py:1068-1096)."""
+    alpha = np.float64(alpha)
+    if alpha == -1.0:
+        nus = np.exp(np.linspace(np.log(lo), np.log(hi), N + 1))
+    else:
+        nus = np.power(np.linspace(lo ** (1 + alpha), hi ** (1 + alpha), N + 1),
+                       (1 + alpha) ** -1)
+    if mid:
+        nus = 0.5 * (nus[:-1] + nus[1:])
+    return nus
+
+
+def fit_powlaw_function(params, freqs, nu_ref, data=None, errs=None):
+    """The weighted residuals (data - powlaw) / errs at params = [A, alpha]
+    (pplib.py:1204-1217; a plain sequence here, lmfit Parameters there)."""
+    A, alpha = params[0], params[1]
+    return (data - powlaw(freqs, nu_ref, A, alpha)) / errs
+
+
+def _chanfit_rows(a, shape):
+    """a broadcast to the [nrow, n] of the data."""
+    return np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), shape), order="C")
+
+
+def fit_powlaws(datas, init_params, errs, freqs, nu_refs):
+    """fit_powlaw on every row of datas [nrow, n] in one device call
+    (ppf_powlaw_fit_rows: Levenberg-Marquardt with leastsq's default ftol and
+    xtol, as lmfit's minimize runs it).  errs and freqs are [nrow, n] or [n],
+    init_params [2] or [nrow, 2] = amplitude at nu_ref, index, nu_refs a
+    scalar or [nrow].  A point whose errs is <= 0, NaN or infinite is left out.
+    Returns a DataBunch of arrays over rows: alpha, alpha_err, amp, amp_err,
+    cov (of amp and alpha), residuals [nrow, n] = data - model, nu_ref, chi2,
+    dof, n_used, status (_lib.CHANFIT_STATUS) and nfev.  A row with fewer than
+    3 usable points or a non-finite value at one of them is NaN."""
+    datas = np.atleast_2d(np.asarray(datas, dtype=np.float64))
+    nrow = datas.shape[0]
+    errs = _chanfit_rows(errs, datas.shape)
+    freqs = _chanfit_rows(freqs, datas.shape)
+    nu_refs = _chanfit_rows(nu_refs, (nrow,))
+    init = _chanfit_rows(init_params, (nrow, 2))
+    out, info = _engine().powlaw_fit_rows(datas, errs, freqs, nu_refs, init)
+    out, info = out.cpu().numpy(), info.cpu().numpy()
+    amp, alpha = out[:, 0], out[:, 2]
+    with np.errstate(all="ignore"):
+        model = powlaw(freqs, nu_refs[:, None], amp[:, None], alpha[:, None])
+    return DataBunch(alpha=alpha, alpha_err=out[:, 3], amp=amp, amp_err=out[:, 1], cov=out[:, 4],
+                     residuals=datas - model, nu_ref=nu_refs, chi2=out[:, 5], dof=info[:, 2],
+                     n_used=info[:, 3], status=info[:, 0], nfev=info[:, 1])
+
+
+def fit_powlaw(data, init_params, errs, freqs, nu_ref):
+    """Fit A (freqs / nu_ref)**alpha to data with uncertainties errs
+    (pplib.py:1763-1802): the one-row case of fit_powlaws.  Returns a DataBunch
+    with alpha, alpha_err, amp, amp_err, residuals = data - model, nu_ref,
+    chi2, dof, and the fit's status and nfev."""
+    data = np.asarray(data, dtype=np.float64)
+    errs = np.broadcast_to(np.asarray(errs, dtype=np.float64), data.shape)
+    r = fit_powlaws(data[None], init_params, errs[None], np.asarray(freqs)[None], nu_ref)
+    return DataBunch(alpha=float(r.alpha[0]), alpha_err=float(r.alpha_err[0]),
+                     amp=float(r.amp[0]), amp_err=float(r.amp_err[0]), residuals=r.residuals[0],
+                     nu_ref=nu_ref, chi2=float(r.chi2[0]), dof=int(r.dof[0]),
+                     status=int(r.status[0]), nfev=int(r.nfev[0]))
+
+
+def fit_DMs_to_freq_resids(freqs, frequency_residuals, errs):
+    """fit_DM_to_freq_resids on every row of frequency_residuals [nrow, n] in
+    one device call (ppf_line_fit_rows); freqs and errs are [nrow, n] or [n],
+    and a point whose errs is <= 0, NaN or infinite is left out.  Returns a
+    DataBunch of arrays over rows with fit_DM_to_freq_resids' fields, plus
+    n_used and status.  dof = n_used - 2 and chi2 sums the used points."""
+    res = np.atleast_2d(np.asarray(frequency_residuals, dtype=np.float64))
+    freqs = _chanfit_rows(freqs, res.shape)
+    errs = _chanfit_rows(errs, res.shape)
+    with np.errstate(all="ignore"):
+        used = (errs > 0.0) & np.isfinite(errs)
+        x = freqs ** -2
+        # the reference hands errs**-2 to polyfit, where 1 / errs would be
+        # the usual weight (pplib.py:1819-1820); kept
+        w = np.where(used, errs, np.inf) ** -2
+        out = _engine().line_fit_rows(x, res, w).cpu().numpy()
+        a, b, a_err, b_err, cov = out[:, 0], out[:, 1], out[:, 2] ** 0.5, out[:, 3] ** 0.5, out[:, 4]
+        nu_ref = (-b / a) ** -0.5
+        nu_ref_err = (((nu_ref ** 2) / 4.0) *
+                      (((a_err / a) ** 2) + ((b_err / b) ** 2) - (2 * cov / (a * b)))) ** 0.5
+        residuals = res - (a[:, None] * x + b[:, None])
+        chi2 = (np.where(used, residuals / np.where(used, errs, 1.0), 0.0) ** 2).sum(axis=1)
+        n_used = out[:, 6].astype(np.int64)
+        dof = n_used - 2
+        chi2 = np.where(np.isnan(a), np.nan, chi2)
+        red_chi2 = chi2 / np.where(dof > 0, dof, 1)
+    return DataBunch(DM=a / Dconst, DM_err=a_err / Dconst, offset=b, offset_err=b_err,
+                     nu_ref=nu_ref, nu_ref_err=nu_ref_err, ab_cov=cov, residuals=residuals,
+                     chi2=chi2, dof=dof, red_chi2=red_chi2, n_used=n_used,
+                     status=out[:, 7].astype(np.int64))
+
+
+def fit_DM_to_freq_resids(freqs, frequency_residuals, errs):
+    """Fit a DM and a reference frequency to residuals [s] across frequency
+    (pplib.py:1804-1840): res = Dconst DM freqs**-2 + offset = Dconst DM
+    (freqs**-2 - nu_ref**-2), by a weighted line in freqs**-2 on the device.
+    ab_cov is the covariance of the line's two coefficients; nu_ref is NaN
+    where -offset / (Dconst DM) < 0."""
+    r = fit_DMs_to_freq_resids(np.asarray(freqs)[None], np.asarray(frequency_residuals)[None],
+                               np.asarray(errs)[None])
+    return DataBunch(DM=float(r.DM[0]), DM_err=float(r.DM_err[0]), offset=float(r.offset[0]),
+                     offset_err=float(r.offset_err[0]), nu_ref=float(r.nu_ref[0]),
+                     nu_ref_err=float(r.nu_ref_err[0]), ab_cov=float(r.ab_cov[0]),
+                     residuals=r.residuals[0], chi2=float(r.chi2[0]), dof=int(r.dof[0]),
+                     red_chi2=float(r.red_chi2[0]))
+
+
 # ---------------------------------------------------------------------------
 # GPU-backed utilities (libppfit)
 # ---------------------------------------------------------------------------

@@ -341,6 +341,39 @@ class DataPortrait(object):
         self.noise_stdsxs = get_noise(self.portx, chans=True)
         self.flux_profx = self.portx.mean(axis=1)
 
+    def fit_flux_profile(self, channel_errs=None, nu_ref=None, guessA=1.0, guessalpha=0.0,
+                         plot=False, savefig=False, quiet=False):
+        """Fit a power law to the phase-averaged flux spectrum of the unzapped
+        channels, flux_profx over freqsxs[0] (pplib.py:426-484), on the
+        device (pplib.fit_powlaw).  channel_errs defaults to ones, nu_ref to
+        nu0.  Sets flux_fit (fit_powlaw's DataBunch), spect_A, spect_A_err,
+        spect_A_ref, spect_index and spect_index_err.  plot defaults to False,
+        unlike the reference: plotting is not part of this build."""
+        if nu_ref is None:
+            nu_ref = self.nu0
+        freqs = np.asarray(self.freqsxs[0], dtype=np.float64)
+        if channel_errs is None:
+            channel_errs = np.ones(len(freqs))
+        fp = pplib.fit_powlaw(self.flux_profx, np.array([guessA, guessalpha]), channel_errs,
+                              freqs, nu_ref)
+        if not quiet:
+            print("")
+            print("Flux-density power-law fit")
+            print("----------------------------------")
+            print("residual mean = %.2f" % fp.residuals.mean())
+            print("residual std. = %.2f" % fp.residuals.std())
+            print("reduced chi-squared = %.2f" % (fp.chi2 / fp.dof))
+            print("A = %.3f +/- %.3f (flux at %.2f MHz)" % (fp.amp, fp.amp_err, fp.nu_ref))
+            print("alpha = %.3f +/- %.3f" % (fp.alpha, fp.alpha_err))
+        if plot or savefig:
+            print("fit_flux_profile: plotting is not part of this build; the fit is in flux_fit")
+        self.flux_fit = fp
+        self.spect_A = fp.amp
+        self.spect_A_err = fp.amp_err
+        self.spect_A_ref = fp.nu_ref
+        self.spect_index = fp.alpha
+        self.spect_index_err = fp.alpha_err
+
     def pca_weights(self):
         """The PCA (and spline) weights of the unzapped channels (ppspline.py:69)."""
         return self.SNRsxs / np.sum(self.SNRsxs)

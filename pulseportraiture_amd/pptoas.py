@@ -13,6 +13,7 @@ import time
 import numpy as np
 
 from . import archive as _arch
+from . import pplib as _pplib
 from .engine import FitPipeline, RawSubints, get_engine
 from .mjd import MJD, add_days_parts, epoch_parts
 from .pplib import (DataBunch, F0_fact, phase_transform, gen_gaussian_portraits_device,
@@ -182,6 +183,14 @@ _LIST_ATTRS = ["obs", "doppler_fs", "nu0s", "nu_fits", "nu_refs", "ok_idatafiles
                "channel_snrs", "profile_fluxes", "profile_flux_errs", "fluxes", "flux_errs",
                "flux_freqs", "red_chi2s", "channel_red_chi2s", "covariances", "nfevals",
                "rcs", "fit_durations", "order", "TOA_list", "zap_channels"]
+# what get_channel_fits leaves, by fit kind: one [nsub] entry per fitted archive
+_CHANFIT_ATTRS = {
+    "nb": ["nb_DMs", "nb_DM_errs", "nb_offsets", "nb_offset_errs", "nb_nu_refs",
+           "nb_nu_ref_errs", "nb_red_chi2s"],
+    "scat": ["scat_amps", "scat_amp_errs", "scat_indices", "scat_index_errs", "scat_nu_refs",
+             "scat_red_chi2s"],
+    "spect": ["spect_As", "spect_A_errs", "spect_indices", "spect_index_errs",
+              "spect_red_chi2s"]}
 
 
 class GetTOAs:
@@ -228,7 +237,7 @@ class GetTOAs:
         self.is_FITS_model = _arch.file_is_type(modelfile, "FITS")
         self.modelfile = modelfile
         self._templates = None
-        for a in _LIST_ATTRS:
+        for a in _LIST_ATTRS + sum(_CHANFIT_ATTRS.values(), []):
             setattr(self, a, [])
         self.TOA_list = TOAList()
         self.instrumental_response_dict = self.ird = {"DM": 0.0, "wids": [], "irf_types": []}
@@ -689,6 +698,125 @@ class GetTOAs:
             tot = time.time() - start
             print("--------------------------")
             print("Total time: %.2f sec, ~%.4f sec/TOA" % (tot, tot / max(len(self.TOA_list), 1)))
+
+    # -- fits across the channels of what the drivers left --------------------
+    def get_channel_fits(self, nu_ref=None, quiet=None):
+        """One measurement per subint from the per-channel values the last
+        driver call left, every subint of every fitted archive in one device
+        call per kind of fit (pplib.fit_DMs_to_freq_resids, pplib.fit_powlaws):
+
+        - after get_narrowband_TOAs: a DM, an offset [s] and the crossing
+          frequency from phis * P with phi_errs * P, over the channels with
+          phi_errs > 0 (fit_DM_to_freq_resids) -> nb_DMs, nb_DM_errs,
+          nb_offsets, nb_offset_errs, nb_nu_refs, nb_nu_ref_errs, nb_red_chi2s;
+        - if that call had fit_scat=True: a power law through the linear
+          scattering times [s] (under log10_tau, tau = 10**t P with sigma =
+          ln 10 tau t_err), over the channels whose error is finite and > 0,
+          from [median tau, pplib.scattering_alpha] -> scat_amps,
+          scat_amp_errs, scat_indices, scat_index_errs, scat_nu_refs,
+          scat_red_chi2s;
+        - after either driver with print_flux=True: a power law through
+          profile_fluxes with profile_flux_errs, over the channels with error
+          > 0, from [mean flux, 0] -> spect_As, spect_A_errs, spect_indices,
+          spect_index_errs, spect_red_chi2s.
+
+        Each list gets one [nsub] entry per fitted archive (the lists are
+        rebuilt by every call); subints that were not fitted, and rows with
+        fewer than 3 usable channels, are NaN.  nu_ref defaults to each
+        archive's nu0.  The lists of a kind that does not apply stay empty; an
+        archive left by the other driver than the last gets NaN entries.  The
+        drivers' own attributes are not touched."""
+        if quiet is None:
+            quiet = self.quiet
+        narch = len(self.order)
+        if not narch:
+            raise RuntimeError("get_channel_fits: no fitted archive; run get_TOAs or "
+                               "get_narrowband_TOAs first")
+        narrow = np.ndim(self.phis[-1]) == 2
+        scat = narrow and bool(getattr(self, "fit_tau", False))
+        flux = any(np.any(np.asarray(e) > 0.0) for e in self.profile_flux_errs)
+        for names in _CHANFIT_ATTRS.values():
+            for a in names:
+                setattr(self, a, [])
+        # the rows: every fitted subint of every archive, padded to the widest
+        freqs, nu_refs, nsubs = [], [], []
+        for name in self.order:
+            meta = self._open(name, getattr(self, "tscrunch", False), True).meta
+            freqs.append(np.asarray(meta.freqs, dtype=np.float64))
+            nu_refs.append(float(meta.nu0) if nu_ref is None else float(nu_ref))
+            nsubs.append(len(freqs[-1]))
+        same = [np.ndim(self.phis[i]) == (2 if narrow else 1) for i in range(narch)]
+        where = [(i, int(isub)) for i in range(narch) if same[i] for isub in self.ok_isubs[i]]
+        nmax = max(f.shape[1] for f in freqs)
+
+        def rows(per_chan, fill):
+            out = np.full((len(where), nmax), fill, dtype=np.float64)
+            for j, (i, isub) in enumerate(where):
+                v = np.asarray(per_chan[i], dtype=np.float64)[isub]
+                out[j, :len(v)] = v
+            return out
+
+        F = rows(freqs, 1.0)
+        P = np.array([self.Ps[i][isub] for i, isub in where], dtype=np.float64)[:, None]
+        nu = np.array([nu_refs[i] for i, _ in where], dtype=np.float64)
+
+        def spread(kind, columns):
+            for a, col in zip(_CHANFIT_ATTRS[kind], columns):
+                vals = [np.full(n, np.nan) for n in nsubs]
+                for j, (i, isub) in enumerate(where):
+                    vals[i][isub] = col[j]
+                getattr(self, a).extend(vals)
+
+        def used_errs(e):
+            with np.errstate(invalid="ignore"):
+                return np.where(np.isfinite(e) & (e > 0.0), e, 0.0)
+
+        def first_guess(y, e, stat):
+            g = np.full(len(y), np.nan)
+            for j in range(len(y)):
+                if (e[j] > 0.0).any():
+                    g[j] = stat(y[j][e[j] > 0.0])
+            return g
+
+        with np.errstate(all="ignore"):
+            if narrow and len(where):
+                e = used_errs(rows(self.phi_errs, 0.0) * P)
+                r = _pplib.fit_DMs_to_freq_resids(F, rows(self.phis, 0.0) * P, e)
+                spread("nb", [r.DM, r.DM_err, r.offset, r.offset_err, r.nu_ref, r.nu_ref_err,
+                              r.red_chi2])
+            if scat and len(where):
+                t, te = rows(self.taus, 0.0), rows(self.tau_errs, 0.0)
+                if self.log10_tau:
+                    tau = 10.0 ** t * P
+                    sig = np.log(10.0) * tau * te
+                else:
+                    tau, sig = t * P, te * P
+                sig = used_errs(sig)
+                init = np.column_stack([first_guess(tau, sig, np.median),
+                                        np.full(len(where), _pplib.scattering_alpha)])
+                r = _pplib.fit_powlaws(tau, init, sig, F, nu)
+                spread("scat", [r.amp, r.amp_err, r.alpha, r.alpha_err, r.nu_ref,
+                                r.chi2 / r.dof])
+            if flux and len(where):
+                y = rows(self.profile_fluxes, 0.0)
+                e = used_errs(rows(self.profile_flux_errs, 0.0))
+                init = np.column_stack([first_guess(y, e, np.mean), np.zeros(len(where))])
+                r = _pplib.fit_powlaws(y, init, e, F, nu)
+                spread("spect", [r.amp, r.amp_err, r.alpha, r.alpha_err, r.chi2 / r.dof])
+        if not quiet:
+            def med(v):
+                v = v[np.isfinite(v)]
+                return np.median(v) if len(v) else np.nan
+
+            for i, name in enumerate(self.order):
+                parts = []
+                if self.nb_DMs:
+                    parts.append("median narrowband DM = %.6f" % med(self.nb_DMs[i]))
+                if self.scat_indices:
+                    parts.append("median scattering index = %.3f" % med(self.scat_indices[i]))
+                if self.spect_indices:
+                    parts.append("median spectral index = %.3f" % med(self.spect_indices[i]))
+                print("%s: %s" % (name, "; ".join(parts) if parts else "no channel fits"))
 
     # -- fitted portraits, residuals and channel zapping --------------------
     def _fitted_rows(self, datafile, isubs, quiet):
